@@ -2,6 +2,7 @@
 """bench.py -- rollout-steps/sec of the MSMP-PDE message-passing rollout step on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--graphs 2048] [--model MSMP-PDE] [--scaling strong|weak]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json configs[1]): E2 (Burgers-type CE, nx=100, time_window=25, radius graph n=3,
@@ -14,14 +15,26 @@ Multi-GPU: graphs are independent, so the batch is shar
 data-path collective.  `--gpus N` without a torchrun environment starts N child processes itself (one per GPU, before
 this process touches the GPU; a process that has initialised the GPU is never exec'd).  The headline at N > 1 is the
 metric's own form, STRONG scaling: the 2048-graph batch split over the ranks (msmp_pde_amd.dist.shard_range), value =
-steps / max-over-ranks time; the same run also measures WEAK scaling (2048 graphs on every rank, object `weak`).
+steps / max-over-ranks time; with --full the same run also measures WEAK scaling (2048 graphs on every rank, object `weak`).
 `--scaling weak` makes the weak number the headline instead.
 
-Extra objects on the JSON line:
-  roofline      dominant kernel (the edge-message kernel): see DESIGN.md section 6.
-  scatter_hbm   row L2 standalone: achieved HBM GB/s of the CSR segmented-mean kernel at the workload's size.
-  cpu_baseline  the CPU oracle (torch-CPU float64 edition, kind "port") timed on this host on a bounded sample.
-  config0       BASELINE.json configs[0] (E2 MP-PDE, 32 graphs): the HIP path and the CPU port side by side.
+A plain run does only what the headline needs: set up, W warm-up steps and the pre-heat, EXACTLY K timed steps, the outputs
+(`--dump-outputs`), one JSON line (`value` in rollout-steps/s, `ms_per_step` = milliseconds of one timed step).
+
+--dump-outputs DIR  after the timed steps, the prediction of the last timed step (what a caller of the step receives, [nodes, tw]
+                    float32) goes to DIR/pred.npy (DIR/pred_rank<r>.npy at N > 1); above 64 MB in all, a fixed seeded sample of
+                    its rows.  Inputs and weights are seeded and the timed window starts at a trajectory restart, so two runs with
+                    the same arguments compute the same step.
+
+--full adds everything else:
+  roofline      dominant kernel (the edge-message kernel), from HIP events around its launches: see DESIGN.md section 6.
+  output_finite config.output_finite: every element of the last prediction is finite.
+  weak/strong   at N > 1 the other scaling mode as a second object (not with --no-extras).
+  scatter_hbm   row L2 standalone: achieved HBM GB/s of the CSR segmented-mean kernel at the workload's size (not with --no-extras).
+  breakdown     forward alone, state update, graph construction (not with --no-extras).
+  config0       BASELINE.json configs[0] (E2 MP-PDE, 32 graphs): the HIP path and the CPU port side by side (not with --no-extras).
+  cpu_baseline  the CPU oracle (torch-CPU float64 edition, kind "port") timed on this host on a bounded sample (not with
+                --no-cpu-baseline).
 """
 import argparse
 import hashlib
@@ -53,8 +66,11 @@ def parse(argv=None):
     ap.add_argument('--experiment', default='E2')
     ap.add_argument('--neighbors', type=int, default=3, help='n of the graph builder (radius n*dx / knn k); 8, 16 = the MSWG3 edge-count stress of SURVEY 8(d)')
     ap.add_argument('--preheat-s', type=float, default=1.0, help='untimed steps run for this long before the timed window (sustained clocks, not boost)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip scatter_hbm / config0 / the second scaling mode (profiling runs)')
+    ap.add_argument('--full', action='store_true', help='also measure and check everything beyond the headline: roofline, scatter_hbm, '
+                                                         'breakdown, config0, cpu_baseline, the second scaling mode (off: a lean run)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write the last timed step\'s prediction to DIR/pred.npy (float32)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(--full) skip cpu_baseline')
+    ap.add_argument('--no-extras', action='store_true', help='(--full) skip scatter_hbm / breakdown / config0 / the second scaling mode (profiling runs)')
     ap.add_argument('--cpu-sample-graphs', type=int, default=128)
     ap.add_argument('--cpu-sample-steps', type=int, default=3)
     ap.add_argument('--dist-backend', default=None, help='torch.distributed backend (default nccl = RCCL); gloo lets ranks share one GPU for testing')
@@ -64,7 +80,10 @@ def parse(argv=None):
     ap.add_argument('--time-all-kernels', action='store_true', help='event-time every kernel family, not only the dominant one')
     ap.add_argument('--launcher-selftest', action='store_true', help='(tests) ranks only join the process group and count themselves; needs no GPU')
     ap.add_argument('--selftest-fail-rank', type=int, default=-1, help='(tests) this rank exits with code 3 before joining the group: the launcher must stop the others')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -179,6 +198,7 @@ def cpu_baseline(model_name, experiment, graphs_total, sample_graphs, sample_ste
 
 class Workload:
     """One rank's share of the batch, resident in HBM, and its rollout step."""
+    TRAJECTORY = 7                                  # rollout steps per unrolled trajectory: steps 75..225 in steps of 25
 
     def __init__(self, args, mp, dev, n_graphs, seed):
         import torch
@@ -201,14 +221,14 @@ class Workload:
         self.pred = self.model(self.graph)
 
     def step(self):
-        step = 75 + 25 * (self.i % 7)               # the reference unrolls steps 75..225 (train_helper.py:255)
+        step = 75 + 25 * (self.i % self.TRAJECTORY)     # the reference unrolls steps 75..225 (train_helper.py:255)
         # ... and starts every unrolled trajectory from ground truth (train_helper.py:243-261): after the 7 steps of one trajectory the
         # next one restarts from the true window.  Same kernels and bytes as a step that feeds the prediction back (the state
         # update assigns whichever tensor it is given); what it avoids is an UNTRAINED network fed its own output for hundreds of
         # steps (WE3: out = u + cumsum(dt) diff with cumsum(dt) up to 10 grows by ~10 per step and leaves the fp16-split path's
         # |x| <= 255 after ~25 steps, at which point Solver.forward switches the model to the exact-fp32 kernels: round 4's
         # range policy; round 3 saturated silently there).
-        src = self.x0 if self.i % 7 == 0 else self.pred
+        src = self.x0 if self.i % self.TRAJECTORY == 0 else self.pred
         self.i += 1
         same = [step] * self.bsz
         _, lab = self.case.creator.create_data(self.case.u_super, same)
@@ -254,7 +274,9 @@ class SplitWorkload:
 
 def timed_run(wl, D, torch, steps, warmup, preheat_s, before_timed=None, after_timed=None):
     """W untimed warm-up steps, `preheat_s` seconds of further untimed steps (so that the timed window runs at the sustained,
-    power-limited clock and not at boost), then EXACTLY `steps` steps between barrier + synchronize brackets."""
+    power-limited clock and not at boost), then EXACTLY `steps` steps between barrier + synchronize brackets.  The untimed steps are
+    rounded up to whole trajectories: the timed window starts at a restart from ground truth whatever the pre-heat ran, so its last
+    step computes the same thing in every run with the same arguments."""
     with torch.no_grad():
         wl.first()
         for _ in range(warmup):
@@ -266,6 +288,10 @@ def timed_run(wl, D, torch, steps, warmup, preheat_s, before_timed=None, after_t
                 wl.step()
             torch.cuda.synchronize()
             n_heat += 4
+        while (warmup + n_heat) % Workload.TRAJECTORY:
+            wl.step()
+            n_heat += 1
+        torch.cuda.synchronize()
         if before_timed:
             before_timed()
         D.barrier()
@@ -279,6 +305,98 @@ def timed_run(wl, D, torch, steps, warmup, preheat_s, before_timed=None, after_t
         if after_timed:
             after_timed()
     return D.reduce_scalar(elapsed, 'max'), n_heat
+
+
+def dump_outputs(directory, pred, rank, world, budget_bytes=64 << 20):
+    """The last timed step's prediction as float32 DIR/pred.npy (DIR/pred_rank<r>.npy at N > 1).  Above the budget (shared by the
+    ranks) a fixed, seeded sample of rows is written instead, in row order: the same rows in every run with the same arguments."""
+    import numpy as np
+    a = pred.detach().float().cpu().numpy()
+    row_bytes = max(a[:1].nbytes, 1)
+    cap = max(budget_bytes // max(world, 1) // row_bytes, 1)
+    if a.shape[0] > cap:
+        a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], cap, replace=False))]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, 'pred.npy' if world == 1 else f'pred_rank{rank}.npy'), np.ascontiguousarray(a))
+
+
+def roofline(args, L, timing, head, split_path):
+    """The `roofline` object (--full): the dominant kernel's launches, event-timed in the timed window, against the MFMA and HBM
+    roofs; see DESIGN.md section 6."""
+    from msmp_pde_amd.graph import structure_of
+    model, graph = timing['model'], timing['graph']
+    n_nodes, n_edges = timing['n_nodes'], timing['n_edges']
+    exp = args.experiment
+    k_msg = model.gnn_layers[0].message_net_1[0].in_features        # 2H + Tw + 1 + nv (Tw = 2*tw for the *2D classes)
+    # Row L1 (message MLP) in the reference's dense formulation: 2*E*K_msg*H + 2*E*H*H per layer (SURVEY 8d).
+    flop_l1_dense = 2.0 * n_edges * k_msg * H + 2.0 * n_edges * H * H
+    n_launch, ms_total = timing['edge']
+    n_proj, ms_proj = timing['proj']
+    t_launch = ms_total / max(n_launch, 1) * 1e-3
+    t_proj = ms_proj / max(n_proj, 1) * 1e-3
+    # Which form ran (DESIGN.md section 4): `folded` = node tiles staged in LDS, P / Q projected inside the message kernel;
+    # `factorised` = separate projection kernel; else the literal per-edge GEMM.
+    tiles = structure_of(graph).tiles()
+    folded = tiles is not None and n_proj == 0 and L.msmp_tune_query(b'tile') == 2 and split_path
+    factorised = folded or n_proj > 0
+    k_tail = 32 * ((k_msg - 2 * H + 31) // 32)                      # [u | pos | vars] columns, padded to whole chunks
+    flop_gemm2 = 2.0 * n_edges * H * H                              # message_net_2: the per-edge GEMM that remains
+    flop_proj_alg = 2.0 * n_nodes * 2 * (H + k_tail) * H            # P and Q of every node once (what the projection kernel executes)
+    # useful fp32 FLOPs of the dominant kernel per launch (no halo recomputation, no padding)
+    flop_exec = (flop_gemm2 + flop_proj_alg) if folded else (flop_gemm2 if factorised else flop_l1_dense)
+    # what the matrix pipe really executes in the folded kernel: one 32-slot node block per tile (halo nodes recomputed, slots padded)
+    flop_pipe = (flop_gemm2 + 2.0 * tiles[0].n_tiles * 32 * 2 * (H + k_tail) * H) if folded else flop_exec
+    achieved = flop_exec / t_launch / 1e12 if n_launch else None
+    alg_tflops = flop_l1_dense / (t_launch + t_proj) / 1e12 if n_launch else None
+    # HBM traffic of the dominant kernel: PMC passes of scripts/profile_gpu.sh, valid only for the sources and workload they were taken on
+    traffic, traffic_note = None, 'no profiles/traffic.json'
+    tpath = os.path.join(ROOT, 'profiles', 'traffic.json')
+    if os.path.exists(tpath):
+        try:
+            tj = json.load(open(tpath))
+            stamp = tj.get('_stamp', {})
+            want = {'source_hash': source_hash(), 'workload': f'{exp}/{args.model}/{head["graphs_this_rank"]}/n{args.neighbors}', 'split': int(split_path)}
+            sym = stamp.get('dominant_kernel')
+            if all(stamp.get(k) == v for k, v in want.items()) and sym in tj:
+                traffic = tj[sym].get('hbm_bytes_per_launch')
+                traffic_note = f'rocprofv3 --pmc FETCH_SIZE (x2, gfx950 correction) + WRITE_SIZE, kernel {sym}, profile {stamp.get("tag")}'
+            else:
+                traffic_note = f'profiles/traffic.json was taken on other sources / workload ({stamp}); not reported'
+        except Exception as exc:                        # noqa: BLE001
+            traffic_note = f'profiles/traffic.json unreadable: {exc}'
+    peak_eq = PEAK_FP16_MFMA_TFLOPS / 3.0 if split_path else PEAK_FP32_MFMA_TFLOPS
+    # algorithmic HBM bytes of the fused message + mean launch (SURVEY 8d "fused layer" accounting for this kernel's share):
+    # read the node rows it consumes once, the CSR, write the aggregate
+    alg_bytes = ((2 * n_nodes * H * 4) if (factorised and not folded) else n_nodes * (H + k_msg - 2 * H) * 4) + n_edges * 4 + (n_nodes + 1) * 4 + n_nodes * H * 4
+    frac_mfma = (achieved / peak_eq) if achieved else None
+    frac_hbm = (alg_bytes / t_launch / 1e9 / PEAK_HBM_GBPS) if n_launch else None
+    # `achieved` counts the USEFUL fp32 GEMM FLOPs the dominant kernel computes (message_net_2 per edge + the per-node projections
+    # once per node; the factorised form removed 69 % of row L1's dense FLOPs).  They execute on the fp16 matrix pipe (2-way fp16 split of both operands, 3 MFMAs per K=16 step, fp32-class
+    # accuracy), so `peak` is that pipe's dense peak / 3 and `frac` equals the literal f16-MFMA utilisation (`matrix_pipe`).
+    # `bound` names the nearer of the two rooflines; `bound_detail` says what the phase profile shows actually limits it.
+    return {'bound': 'mfma' if (frac_mfma or 0) >= (frac_hbm or 0) else 'hbm',
+            'bound_detail': 'neither roof: see DESIGN.md section 4 (phase profile: node-row gather latency, LDS port and activation VALU; matrix pipe and HBM both under 0.4)',
+            'kernel': 'edge message kernel (message_net_2 + Swish + per-target mean'
+            + (', node tiles staged in LDS with the per-node projections of message_net_1 folded in' if folded
+               else ', factorised message_net_1 (separate projection kernel)' if factorised else ', dense message_net_1')
+            + ('; fp32 GEMM on the fp16 matrix pipe via 2-way fp16 split)' if split_path else '; fp32 MFMA)'),
+            'achieved': achieved, 'peak': peak_eq,
+            'unit': 'TFLOP/s', 'frac': frac_mfma,
+            'peak_note': ('fp32-equivalent peak of the 3-MFMA fp16 split = dense f16 MFMA peak / 3' if split_path
+                          else 'dense fp32 MFMA peak'),
+            'vs_fp32_mfma_peak': (achieved / PEAK_FP32_MFMA_TFLOPS) if achieved else None,
+            'hbm': {'algorithmic_bytes_per_launch': alg_bytes, 'achieved_GBps': alg_bytes / t_launch / 1e9 if n_launch else None,
+                    'peak_GBps': PEAK_HBM_GBPS, 'frac': frac_hbm},
+            'traffic': traffic, 'traffic_note': traffic_note, 'launches': n_launch, 'avg_launch_ms': t_launch * 1e3,
+            'executed_gflop_per_launch': flop_exec / 1e9,
+            'matrix_pipe': ({'dtype': 'f16 (3 MFMAs per fp32 K=16 step)', 'executed_tflops': 3 * flop_pipe / t_launch / 1e12,
+                             'peak_tflops': PEAK_FP16_MFMA_TFLOPS, 'frac': 3 * flop_pipe / t_launch / 1e12 / PEAK_FP16_MFMA_TFLOPS,
+                             'note': 'everything the pipe executes, incl. halo recomputation and padded node slots of the folded projections'}
+                            if split_path and achieved else None),
+            'algorithmic': {'row': 'L1+L2 message MLP + mean = node projection + message kernels per layer',
+                            'gflop_per_layer': flop_l1_dense / 1e9, 'ms_per_layer': (t_launch + t_proj) * 1e3,
+                            'tflops': alg_tflops, 'frac': alg_tflops / PEAK_FP32_MFMA_TFLOPS if alg_tflops else None},
+            'share_of_step': (ms_total / timing['steps']) / head['ms_per_step'] if n_launch else None}
 
 
 def run_rank(args):
@@ -315,7 +433,7 @@ def run_rank(args):
         return 2
 
     modes = ['strong', 'weak'] if args.scaling == 'strong' else ['weak', 'strong']
-    if world == 1 or args.no_extras:
+    if world == 1 or args.no_extras or not args.full:
         modes = modes[:1]
     results = {}
     timing = {}
@@ -330,6 +448,7 @@ def run_rank(args):
         parts = args.sub_batches if args.sub_batches > 0 else (2 if n_graphs <= 1024 and n_graphs >= 64 else 1)
         wl = SplitWorkload(args, mp, dev, n_graphs, 1000 + rank, parts) if parts > 1 else Workload(args, mp, dev, n_graphs, seed=1000 + rank)
         head = mode == modes[0]
+        events = head and (args.full or args.time_all_kernels)        # HIP events around the kernels' launches (roofline, per-kernel ms)
 
         def start_events():
             mask = 0b1111111 if args.time_all_kernels else (1 << _lib.K_EDGE_MLP) | (1 << _lib.K_NODE_PROJ)
@@ -337,9 +456,11 @@ def run_rank(args):
             L.msmp_timing_enable(mask)
 
         elapsed, n_heat = timed_run(wl, D, torch, args.steps if head else max(args.steps // 2, 5), args.warmup, args.preheat_s,
-                                    start_events if head else None, (lambda: L.msmp_timing_enable(0)) if head else None)
+                                    start_events if events else None, (lambda: L.msmp_timing_enable(0)) if events else None)
         k_steps = args.steps if head else max(args.steps // 2, 5)
-        finite = bool(torch.isfinite(wl.pred).all().item())
+        if head and args.dump_outputs:
+            dump_outputs(args.dump_outputs, wl.pred, rank, world)
+        finite = bool(torch.isfinite(wl.pred).all().item()) if args.full else None
         graphs_all = int(round(D.reduce_scalar(n_graphs, 'sum')))
         # strong: a step advances the ONE shared batch, so steps/s = K / t.  weak: every rank advances its own batch: N K / t.
         value = k_steps / elapsed if mode == 'strong' else world * k_steps / elapsed
@@ -347,7 +468,7 @@ def run_rank(args):
                          'steps': k_steps, 'graph_steps_per_s': graphs_all * k_steps / elapsed, 'output_finite': finite, 'preheat_steps': n_heat,
                          'range_exact': bool(getattr(wl.model, '_range_exact', False))}
         if head:
-            timing = {'edge': _lib.timing_read(_lib.K_EDGE_MLP), 'proj': _lib.timing_read(_lib.K_NODE_PROJ),
+            timing = {'edge': _lib.timing_read(_lib.K_EDGE_MLP) if events else (0, 0.0), 'proj': _lib.timing_read(_lib.K_NODE_PROJ) if events else (0, 0.0),
                       'n_nodes': wl.n_nodes // parts, 'n_edges': wl.n_edges // parts, 'sub_batches': parts, 'model': wl.model, 'graph': wl.graph, 'steps': k_steps,
                       'all': ({k: _lib.timing_read(k) for k in range(7)} if args.time_all_kernels else None)}
             head_wl = wl
@@ -362,50 +483,6 @@ def run_rank(args):
     n_nodes, n_edges = timing['n_nodes'], timing['n_edges']
     kind = type(model).__name__
     exp = args.experiment
-    k_msg = model.gnn_layers[0].message_net_1[0].in_features        # 2H + Tw + 1 + nv (Tw = 2*tw for the *2D classes)
-    # Row L1 (message MLP) in the reference's dense formulation: 2*E*K_msg*H + 2*E*H*H per layer.
-    flop_l1_dense = 2.0 * n_edges * k_msg * H + 2.0 * n_edges * H * H
-    n_launch, ms_total = timing['edge']
-    n_proj, ms_proj = timing['proj']
-    t_launch = ms_total / max(n_launch, 1) * 1e-3
-    t_proj = ms_proj / max(n_proj, 1) * 1e-3
-    # Which form ran: `folded` = node tiles staged in LDS, P / Q projected inside the message kernel;
-    # `factorised` = separate projection kernel; else the literal per-edge GEMM.
-    from msmp_pde_amd.graph import structure_of
-    tiles = structure_of(graph).tiles()
-    folded = tiles is not None and n_proj == 0 and L.msmp_tune_query(b'tile') == 2 and split_path
-    factorised = folded or n_proj > 0
-    k_tail = 32 * ((k_msg - 2 * H + 31) // 32)                      # [u | pos | vars] columns, padded to whole chunks
-    flop_gemm2 = 2.0 * n_edges * H * H                              # message_net_2: the per-edge GEMM that remains
-    flop_proj_alg = 2.0 * n_nodes * 2 * (H + k_tail) * H            # P and Q of every node once (what the projection kernel executes)
-    # useful fp32 FLOPs of the dominant kernel per launch (no halo recomputation, no padding)
-    flop_exec = (flop_gemm2 + flop_proj_alg) if folded else (flop_gemm2 if factorised else flop_l1_dense)
-    # what the matrix pipe really executes in the folded kernel: one 32-slot node block per tile (halo nodes recomputed, slots padded)
-    flop_pipe = (flop_gemm2 + 2.0 * tiles[0].n_tiles * 32 * 2 * (H + k_tail) * H) if folded else flop_exec
-    achieved = flop_exec / t_launch / 1e12 if n_launch else None
-    alg_tflops = flop_l1_dense / (t_launch + t_proj) / 1e12 if n_launch else None
-    # HBM traffic of the dominant kernel: PMC passes of scripts/profile_gpu.sh, valid only for the sources and workload they were taken on
-    traffic, traffic_note = None, 'no profiles/traffic.json'
-    tpath = os.path.join(ROOT, 'profiles', 'traffic.json')
-    if os.path.exists(tpath):
-        try:
-            tj = json.load(open(tpath))
-            stamp = tj.get('_stamp', {})
-            want = {'source_hash': source_hash(), 'workload': f'{exp}/{args.model}/{head["graphs_this_rank"]}/n{args.neighbors}', 'split': int(split_path)}
-            sym = stamp.get('dominant_kernel')
-            if all(stamp.get(k) == v for k, v in want.items()) and sym in tj:
-                traffic = tj[sym].get('hbm_bytes_per_launch')
-                traffic_note = f'rocprofv3 --pmc FETCH_SIZE (x2, gfx950 correction) + WRITE_SIZE, kernel {sym}, profile {stamp.get("tag")}'
-            else:
-                traffic_note = f'profiles/traffic.json was taken on other sources / workload ({stamp}); not reported'
-        except Exception as exc:                        # noqa: BLE001
-            traffic_note = f'profiles/traffic.json unreadable: {exc}'
-    peak_eq = PEAK_FP16_MFMA_TFLOPS / 3.0 if split_path else PEAK_FP32_MFMA_TFLOPS
-    # algorithmic HBM bytes of the fused message + mean launch (SURVEY 8d "fused layer" accounting for this kernel's share):
-    # read the node rows it consumes once, the CSR, write the aggregate
-    alg_bytes = ((2 * n_nodes * H * 4) if (factorised and not folded) else n_nodes * (H + k_msg - 2 * H) * 4) + n_edges * 4 + (n_nodes + 1) * 4 + n_nodes * H * 4
-    frac_mfma = (achieved / peak_eq) if achieved else None
-    frac_hbm = (alg_bytes / t_launch / 1e9 / PEAK_HBM_GBPS) if n_launch else None
     out = {
         'metric': 'rollout-steps/sec (whole node), E2 nx=100 tw=25',
         'value': head['value'], 'unit': 'rollout-steps/s', 'n_gpus': world, 'steps': args.steps,
@@ -419,38 +496,13 @@ def run_rank(args):
                    'sub_batches': timing.get('sub_batches', 1),
                    'graph_steps_per_s': head['graph_steps_per_s'],
                    'edge_steps_per_s': head['graph_steps_per_s'] * n_edges / max(head['graphs_this_rank'], 1),
-                   'output_finite': head['output_finite'],
+                   **({'output_finite': head['output_finite']} if args.full else {}),
                    # True would mean the range policy moved the model to the exact-fp32 kernels inside the run (data left |x| <= 255): not the path this line is about
                    'range_policy_switched_to_exact_fp32': head['range_exact'],
                    'preheat': f'{head["preheat_steps"]} untimed steps (>= {args.preheat_s:g} s) after the {args.warmup} warm-up steps'},
-        # `achieved` counts the USEFUL fp32 GEMM FLOPs the dominant kernel computes (message_net_2 per edge + the per-node projections
-        # once per node; the factorised form removed 69 % of row L1's dense FLOPs).  They execute on the fp16 matrix pipe (2-way fp16 split of both operands, 3 MFMAs per K=16 step, fp32-class
-        # accuracy), so `peak` is that pipe's dense peak / 3 and `frac` equals the literal f16-MFMA utilisation (`matrix_pipe`).
-        # `bound` names the nearer of the two rooflines; `bound_detail` says what the phase profile shows actually limits it.
-        'roofline': {'bound': 'mfma' if (frac_mfma or 0) >= (frac_hbm or 0) else 'hbm',
-                     'bound_detail': 'neither roof: see DESIGN.md section 4 (phase profile: node-row gather latency, LDS port and activation VALU; matrix pipe and HBM both under 0.4)',
-                     'kernel': 'edge message kernel (message_net_2 + Swish + per-target mean'
-                     + (', node tiles staged in LDS with the per-node projections of message_net_1 folded in' if folded
-                        else ', factorised message_net_1 (separate projection kernel)' if factorised else ', dense message_net_1')
-                     + ('; fp32 GEMM on the fp16 matrix pipe via 2-way fp16 split)' if split_path else '; fp32 MFMA)'),
-                     'achieved': achieved, 'peak': peak_eq,
-                     'unit': 'TFLOP/s', 'frac': frac_mfma,
-                     'peak_note': ('fp32-equivalent peak of the 3-MFMA fp16 split = dense f16 MFMA peak / 3' if split_path
-                                   else 'dense fp32 MFMA peak'),
-                     'vs_fp32_mfma_peak': (achieved / PEAK_FP32_MFMA_TFLOPS) if achieved else None,
-                     'hbm': {'algorithmic_bytes_per_launch': alg_bytes, 'achieved_GBps': alg_bytes / t_launch / 1e9 if n_launch else None,
-                             'peak_GBps': PEAK_HBM_GBPS, 'frac': frac_hbm},
-                     'traffic': traffic, 'traffic_note': traffic_note, 'launches': n_launch, 'avg_launch_ms': t_launch * 1e3,
-                     'executed_gflop_per_launch': flop_exec / 1e9,
-                     'matrix_pipe': ({'dtype': 'f16 (3 MFMAs per fp32 K=16 step)', 'executed_tflops': 3 * flop_pipe / t_launch / 1e12,
-                                      'peak_tflops': PEAK_FP16_MFMA_TFLOPS, 'frac': 3 * flop_pipe / t_launch / 1e12 / PEAK_FP16_MFMA_TFLOPS,
-                                      'note': 'everything the pipe executes, incl. halo recomputation and padded node slots of the folded projections'}
-                                     if split_path and achieved else None),
-                     'algorithmic': {'row': 'L1+L2 message MLP + mean = node projection + message kernels per layer',
-                                     'gflop_per_layer': flop_l1_dense / 1e9, 'ms_per_layer': (t_launch + t_proj) * 1e3,
-                                     'tflops': alg_tflops, 'frac': alg_tflops / PEAK_FP32_MFMA_TFLOPS if alg_tflops else None},
-                     'share_of_step': (ms_total / timing['steps']) / head['ms_per_step'] if n_launch else None},
     }
+    if args.full:
+        out['roofline'] = roofline(args, L, timing, head, split_path)
     if len(modes) > 1:
         other = results[modes[1]]
         out[modes[1]] = {'value': other['value'], 'unit': 'rollout-steps/s', 'ms_per_step': other['ms_per_step'], 'steps': other['steps'],
@@ -463,7 +515,7 @@ def run_rank(args):
                  _lib.K_LEM: 'lem_encoder', _lib.K_NODE_PROJ: 'node_project', _lib.K_DECODER: 'decoder'}
         out['kernels_ms_per_step'] = {nm: timing['all'][k][1] / timing['steps'] for k, nm in names.items()}
         out['kernels_launches_per_step'] = {nm: timing['all'][k][0] / timing['steps'] for k, nm in names.items()}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # row L2 standalone ("HBM GB/s on the scatter"): the default layer path fuses the mean into the message kernel,
         # so the CSR segmented-mean kernel is timed here on a message tensor of the workload's size, outside the timed region
         from msmp_pde_amd.graph import structure_of
@@ -511,7 +563,7 @@ def run_rank(args):
                             'note': 'forward_only = model(graph) alone; state_update = create_data labels + create_next_graph (the rest of a step); '
                                     'graph_construction = create_data + create_graph (radius / knn graph on the device) + CSR + node tiles, once per rollout, '
                                     'not part of a step'}
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         # BASELINE.json configs[0]: E2 MP-PDE on 32 graphs (the reference's own CPU-runnable case), HIP path and CPU port
         a0 = parse(['--model', 'MP-PDE', '--experiment', 'E2', '--graphs', '32'])
         wl0 = Workload(a0, mp, dev, 32, seed=1000)
@@ -521,7 +573,7 @@ def run_rank(args):
         if not args.no_cpu_baseline:
             out['config0']['cpu_baseline'] = cpu_baseline('MP-PDE', 'E2', 32, 32, 5)
         del wl0
-    if not args.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only
+    if args.full and not args.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only
         out['cpu_baseline'] = cpu_baseline(args.model, exp, args.graphs, args.cpu_sample_graphs, args.cpu_sample_steps, args.neighbors)
     print(json.dumps(out), flush=True)
     return 0

@@ -8,7 +8,7 @@ res = {l: [] for l in libs}
 for r in range(rounds):
     for l in libs:
         env = dict(os.environ, MSMP_LIB_PATH=os.path.join(ROOT, 'msmp-pde_amd', l))
-        out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '40', '--warmup', '3', '--no-cpu-baseline', '--no-extras'],
+        out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '40', '--warmup', '3', '--full', '--no-cpu-baseline', '--no-extras'],
                              env=env, capture_output=True, text=True)
         d = json.loads([x for x in out.stdout.splitlines() if x.startswith('{')][-1])
         res[l].append((round(d['ms_per_step'], 3), round(d['roofline']['avg_launch_ms'] * 1e3, 1)))

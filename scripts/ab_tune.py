@@ -11,7 +11,7 @@ res = {s: [] for s in sets}
 for r in range(rounds):
     for s in sets:
         tune = [x for kv in s.split(',') if kv for x in ('--tune', kv)]
-        out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '40', '--warmup', '3', '--no-cpu-baseline', '--no-extras'] + extra + tune,
+        out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '40', '--warmup', '3', '--full', '--no-cpu-baseline', '--no-extras'] + extra + tune,
                              capture_output=True, text=True)
         lines = [x for x in out.stdout.splitlines() if x.startswith('{')]
         if not lines:

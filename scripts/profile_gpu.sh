@@ -19,7 +19,7 @@ json.dump({'source_hash': bench.source_hash(), 'workload': f'{a.experiment}/{a.m
           open(os.path.join(sys.argv[1], 'stamp.json'), 'w'))
 PY
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --steps 5 --warmup 2 --preheat-s 0.3 --no-cpu-baseline --no-extras "$@" > $OUT/trace.log 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --steps 5 --warmup 2 --preheat-s 0.3 --full --no-cpu-baseline --no-extras "$@" > $OUT/trace.log 2>&1 || exit 1
 grep '^{' $OUT/trace.log > $OUT/trace_bench.json
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python3 $R/bench.py --steps 2 --warmup 1 --preheat-s 0 --no-cpu-baseline --no-extras "$@" > $OUT/pmc_fetch.log 2>&1 || exit 1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- python3 $R/bench.py --steps 2 --warmup 1 --preheat-s 0 --no-cpu-baseline --no-extras "$@" > $OUT/pmc_write.log 2>&1 || exit 1

@@ -315,6 +315,30 @@ def test_bench_launcher_stops_the_other_ranks_when_one_fails():
     assert 'rank 1 exited with code 3' in r.stderr and '[rank 1] selftest: this rank fails on purpose' in r.stderr
 
 
+def test_bench_dump_outputs_and_options(tmp_path):
+    """bench.py --dump-outputs: float32 DIR/pred.npy holding the prediction as is; above the byte budget the same seeded rows in
+    every call, in row order; one file per rank at N > 1.  --full is off by default and --steps must be positive."""
+    sys.path.insert(0, ROOT)
+    import bench
+    pred = torch.randn(2000, 25, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / 'a'), pred, 0, 1)
+    a = np.load(tmp_path / 'a' / 'pred.npy')
+    assert a.dtype == np.float32 and np.array_equal(a, pred.float().numpy())
+    for d in ('b', 'c'):
+        bench.dump_outputs(str(tmp_path / d), pred, 0, 1, budget_bytes=100 * 25 * 4)
+    b, c = np.load(tmp_path / 'b' / 'pred.npy'), np.load(tmp_path / 'c' / 'pred.npy')
+    assert b.shape == (100, 25) and np.array_equal(b, c)
+    rows = [int(np.flatnonzero((a == r).all(1))[0]) for r in b]
+    assert rows == sorted(rows)
+    bench.dump_outputs(str(tmp_path / 'd'), pred, 1, 2)
+    assert os.listdir(tmp_path / 'd') == ['pred_rank1.npy']
+    args = bench.parse(['--steps', '7', '--warmup', '2'])
+    assert not args.full and args.dump_outputs is None and args.steps == 7
+    assert bench.parse(['--full', '--dump-outputs', 'x']).full
+    with pytest.raises(SystemExit):
+        bench.parse(['--steps', '0'])
+
+
 def test_decoder_convolution_as_toeplitz_gemm_matches_conv1d():
     """solvers._conv1d_as_matmul (the AUTOGRAD decoder: Conv1d as one dense GEMM against the convolution's Toeplitz matrix, itself the
     weight times a fixed shift tensor) against torch.nn.functional.conv1d, forward and all three gradients, for every decoder geometry
