@@ -77,7 +77,8 @@ const char* msmp_last_error(void);
 int msmp_last_status(int* flags_out, int reset);
 /* Knobs for A/B measurements and validation (not part of the data contract):
  *   "split"   1 (default): the GEMMs of the node / edge / LEM kernels run on the fp16 matrix pipe with a 2-way
- *             fp16 split of both operands (fp32-class accuracy); 0: the fp32-MFMA kernels.
+ *             fp16 split of both operands (fp32-class accuracy); 0: the fp32-MFMA kernels.  It also selects
+ *             the LEM kernel: 1 the weight-stationary lem_encoder_ws3_kernel, 0 the fp32 lem_encoder_kernel.
  *   "edge_nb" 0 auto, 1 / 2 force the 128- / 256-edge tile of the factorised message kernel.
  *   "tile"    2 (default): with node tiles that are at least 60 % full (>= 76 edges per tile on average), project P / Q inside the message
  *             kernel, else the gather kernels; 3: the same regardless of the fill; 1: msmp_node_project_f32 + tile kernel on the
@@ -91,9 +92,7 @@ int msmp_last_status(int* flags_out, int reset);
  *   "tile_arith" 1 (default): ranged tiles take their node rows by arithmetic on tile_halo; 0: always through the node list.
  *   "tail"    1 (default): msmp_mp_layer_f32 uses msmp_node_tail_f32 for graphs of up to 128 nodes; 0: the piecewise kernels.
  *   "pair"    gated pair: both heads' projection / message kernels in one launch each (bit-identical results): 0 never,
- *             1 (default) for batches of up to 65 536 nodes, where a step is bound by the latency of its ~60 dependent launches, 2 always.
- *   "lem"     LEM encoder edition: 4 (default) weight-stationary, three node tiles, matrix / vector halves of a SIMD's two waves in
- *             anti-phase; 3 the two-tile weight-stationary kernel of round 2; 0 fp32 MFMA ("split" 1 / 0 selects 4 / 0). */
+ *             1 (default) for batches of up to 65 536 nodes, where a step is bound by the latency of its ~60 dependent launches, 2 always. */
 int msmp_tune(const char* key, int value);
 int msmp_tune_query(const char* key);      /* current value of "split", "tail", "pair", "bwd_gemm", "tile", "tile_arith" (0 for other keys) */
 
@@ -370,7 +369,7 @@ int msmp_linear_swish_f32(const float* x, int64_t rows, int k, const float* w, c
  *   two_d = 0: x_t = [pos_x, u_t, variables]                                experiments/models_gnn.py:1357-1360, ninp = 2 + nv
  *   two_d = 1: x_t = [pos_x, u_t, u_{tw+t}, dt_cum_t + pos_t, variables[1:]]  experiments/models_gnn2D.py:429-433, ninp = 3 + nv
  * u [N, tw] ([N, 2 tw] for two_d), pos_x / pos_t [N], vars [N, nv] (column 0 = pos_t), dt_cum [tw] = cumsum(pde.dt);
- * `packed` from msmp_pack_lem_f32 with that ninp.  MSMP_ERR_UNSUPPORTED unless the weight-stationary edition is selected. */
+ * `packed` from msmp_pack_lem_f32 with that ninp.  MSMP_ERR_UNSUPPORTED on the exact-fp32 path (msmp_tune("split", 0)). */
 int msmp_lem_encoder_nodes_f32(const float* u, const float* pos_x, const float* pos_t, const float* vars, const float* dt_cum,
                                int64_t n_nodes, int tw, int nv, int two_d, float dt, const float* packed, int with_mlp,
                                float* h_out, msmp_stream_t stream);

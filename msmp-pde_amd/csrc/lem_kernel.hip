@@ -278,23 +278,28 @@ __global__ __launch_bounds__(256) void lem_encoder_kernel(LemArgs a) {
 
 
 // ----------------------------------------------------------------------------------------------
-// WEIGHT-STATIONARY edition (default).  The recurrent weights (4 gates x [128 x 128], fp16 hi + lo = 256 KB) fit the
-// CU's register file: a 512-thread workgroup = 4 channel slices x 2 roles, and wave (ks, role) keeps the hi/lo A
-// fragments of TWO gate tiles (rows 32 ks .. 32 ks + 31; 128 registers) for the whole kernel:
+// WEIGHT-STATIONARY, ANTI-PHASED kernel (lem_encoder_ws3_kernel: the fp16-split path; msmp_tune("split", 0) selects the fp32 kernel
+// above).  The recurrent weights (4 gates x [128 x 128], fp16 hi + lo = 256 KB) fit the CU's register file: a 512-thread workgroup =
+// 4 channel slices x 2 roles, and wave (ks, role) keeps the hi/lo A fragments of TWO gate tiles (rows 32 ks .. 32 ks + 31; 128
+// registers) for the whole kernel:
 //     role A: g2 (dt_) and g3 (z candidate)  ->  z <- z + dt s(g2) (tanh(g3) - z)      (owns the z slice)
 //     role B: g1 (dt_bar) and lin            ->  y <- y + dt s(g1) (tanh(lin) - y)     (owns the y slice)
-// so each state update is wave-local, no weight ever moves after the prologue, and the only LDS traffic is the
-// hi/lo state fragments every wave publishes for its 32 channels and all waves read as B operands (0.3 KB per MFMA
-// instead of 1 KB with streamed weights, which had the LDS port as busy as the matrix pipe).  A workgroup carries
-// two node tiles (64 nodes) in a two-stage software pipeline, one barrier per stage:
-//     stage 2t + X:     role A works on (tile X, step t):   reads y_X(t),             publishes z_X(t+1)
-//     stage 2t + X + 1: role B works on (tile X, step t):   reads y_X(t), z_X(t+1),   publishes y_X(t+1)
-// (y is double-buffered in LDS because role-B waves still read y_X(t) while others publish y_X(t+1)).  Both waves of a
-// SIMD always have two gate GEMMs (48 + input MFMAs) and 16 registers of activations per stage, and one's VALU
-// overlaps the other's matrix work.  The input columns W[:, H:] x_t are one K=16 fp16 MFMA per gate for ninp <= 5
+// so each state update is wave-local, no weight ever moves after the prologue, and the only LDS traffic is the hi/lo state fragments
+// every wave publishes for its 32 channels and all waves read as B operands (0.3 KB per MFMA instead of 1 KB with streamed weights,
+// which had the LDS port as busy as the matrix pipe).  The input columns W[:, H:] x_t are one K=16 fp16 MFMA per gate for ninp <= 5
 // (two for ninp <= 8) through the slot pairing of lem_slot_feature.  s(a) tanh(b) is evaluated with ONE reciprocal:
 //     e_a = 2^(-a log2 e), e_b = 2^(-2 b log2 e), r = 1 / ((1 + e_a)(1 + e_b)):   st += dt r ((1 - e_b) - st (1 + e_b))
 // (exponents clamped at 60 so the product stays finite).
+// A workgroup carries THREE node tiles (96 nodes) and every work item is cut into its matrix half M (input MFMAs + the two gate
+// GEMMs: 50 MFMAs, accumulators kept in registers) and its vector half V (state update + publish), one barrier per half.  The two
+// waves of a SIMD are wave (ks, A) and wave (ks, B); per time step t and slot j = 0..5:
+//     role A:  M(0,t)    V(0,t)     M(1,t)     V(1,t)   M(2,t)   V(2,t)
+//     role B:  V(1,t-1)  M(2,t-1)   V(2,t-1)   M(0,t)   V(0,t)   M(1,t)
+// so one wave of every SIMD is in a matrix half while the other is in a vector half (with matrix beside matrix and vector beside
+// vector, a SIMD spent 6.7 k cycles per tile pair and step for 3.2 k cycles of matrix work: rocprofv3 SQ counters, profiles/r03c_*).
+// Dependencies (A's V(X,t) publishes z_X(t+1), read by B's M(X,t); B's V(X,t) publishes y_X(t+1), read by A's M(X,t+1) and B's
+// M(X,t+1)) are each separated by at least one barrier, and every buffer's last reader precedes its next writer by a barrier, so y
+// needs ONE buffer per tile.
 // ----------------------------------------------------------------------------------------------
 struct LemWsArgs {
     const float* xin;       // MODE 0: [N, T, 2*NS] assembled step inputs
@@ -422,76 +427,14 @@ __device__ __forceinline__ float vmin(float a, float b) {            // bare v_m
     asm("v_min_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
     return d;
 }
-struct LemActConst {
-    f32x2 c0, c1, idt, one;
-};
 
-// st <- st + dt s(a0) (tanh(a1) - st) for one [32 x 32] tile, then publish it as hi/lo B fragments of K tile `ks`.
-// One reciprocal per value: e_a = 2^(c0 a0), e_b = 2^(min(c1 a1, 60)), r = dt / ((1 + e_a)(1 + e_b)),
-// st += r ((1 - e_b) - st (1 + e_b)); e_a = inf gives r = 0 (st unchanged), the clamp keeps (1 - e_b) r finite.
-__device__ __forceinline__ void lem_ws_update_publish(const f32x16& a0, const f32x16& a1, const LemActConst& k, f32x16& st,
-                                                      half8* area, int ks, int lane) {
-    // Staged per half tile, with scheduling barriers between the stages: the compiler's hazard recogniser does not look
-    // inside inline asm, so an accumulator (MFMA result) is first touched by a compiler-emitted multiply, and every
-    // transcendental result is consumed a whole stage later.
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        f32x2 ta[4], tb[4], ea[4], eb[4], qb[4], q[4], rr[4];
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            const int r = 8 * s + 2 * jj;
-            ta[jj] = f32x2{a0[r] * k.c0[0], a0[r + 1] * k.c0[0]};
-            tb[jj] = f32x2{fminf(a1[r] * k.c1[0], 60.f), fminf(a1[r + 1] * k.c1[0], 60.f)};
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            ea[jj] = f32x2{msmp_exp2(ta[jj][0]), msmp_exp2(ta[jj][1])};
-            eb[jj] = f32x2{msmp_exp2(tb[jj][0]), msmp_exp2(tb[jj][1])};
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            qb[jj] = pk_add(eb[jj], k.one);
-            q[jj] = pk_mul(pk_fma(ea[jj], k.idt, k.idt), qb[jj]);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) rr[jj] = f32x2{msmp_rcp(q[jj][0]), msmp_rcp(q[jj][1])};
-        f32x2 tt[4];
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            const int r = 8 * s + 2 * jj;
-            tt[jj] = pk_fnma(f32x2{st[r], st[r + 1]}, qb[jj], pk_sub(k.one, eb[jj]));
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        half8 phi, plo;
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            const int r = 8 * s + 2 * jj;
-            const f32x2 sv = pk_fma(rr[jj], tt[jj], f32x2{st[r], st[r + 1]});
-            st[r] = sv[0];
-            st[r + 1] = sv[1];
-            const half2 hp = __builtin_convertvector(sv, half2);
-            const half2 lp = split_lo_pair(hp, sv);
-            phi[2 * jj] = hp[0];
-            phi[2 * jj + 1] = hp[1];
-            plo[2 * jj] = lp[0];
-            plo[2 * jj + 1] = lp[1];
-        }
-        area[((ks * 2 + s) * 2 + 0) * 64 + lane] = phi;
-        area[((ks * 2 + s) * 2 + 1) * 64 + lane] = plo;
-    }
-}
-
-// The state update of the anti-phased kernel: plain (unpacked) fp32 instructions.  Its vector halves run BESIDE the partner wave's
-// MFMAs, where a packed-fp32 instruction (v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32) waits for the matrix pipe: measured 2 700
-// cycles per vector half with the packed form of lem_ws_update_publish against 1 500 for the matrix half (scripts/prof_lem.py).
-// Two value pairs per stage (half the live temporaries of lem_ws_update_publish: this kernel keeps a work item's accumulators
-// across a barrier and one more state tile).
-__device__ __forceinline__ void lem_ws_update_publish_q(const f32x16& a0, const f32x16& a1, const LemActConst& k, f32x16& st,
+// st <- st + dt s(a0) (tanh(a1) - st) for one [32 x 32] tile, then publish it as hi/lo B fragments of K tile `ks`.  One reciprocal per
+// value: e_a = 2^(c0 a0), e_b = 2^(min(c1 a1, 60)), r = dt / ((1 + e_a)(1 + e_b)), st += r ((1 - e_b) - st (1 + e_b)); e_a = inf gives
+// r = 0 (st unchanged), the clamp keeps (1 - e_b) r finite.  Plain (unpacked) fp32 instructions: the vector halves run BESIDE the
+// partner wave's MFMAs, where a packed-fp32 instruction (v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32) waits for the matrix pipe:
+// measured 2 700 cycles per vector half with a packed form against 1 500 for the matrix half (scripts/prof_lem.py).
+__device__ __forceinline__ void lem_ws_update_publish_q(const f32x16& a0, const f32x16& a1, float c0, float c1, float idt, f32x16& st,
                                                         half8* area, int ks, int lane) {
-    const float c0 = k.c0[0], c1 = k.c1[0], idt = k.idt[0];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
         half8 phi, plo;
@@ -524,222 +467,7 @@ __device__ __forceinline__ void lem_ws_update_publish_q(const f32x16& a0, const 
 
 // sched_barrier mask: everything may cross except MFMAs (and the catch-all ALU class that contains them)
 constexpr int LEM_SCHED_NOT_MFMA = 0x7F6;
-// acc0 += W0 B0, acc1 += W1 B1 over K = 128 (B0/B1: published fragment areas; they may be the same area)
-template <bool SAME>
-__device__ __forceinline__ void lem_ws_gemm2(const half8 (&w0)[4][2][2], const half8 (&w1)[4][2][2], const half8* b0, const half8* b1,
-                                             int lane, f32x16& acc0, f32x16& acc1) {
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const half8 h0 = b0[((kt * 2 + s) * 2 + 0) * 64 + lane], l0 = b0[((kt * 2 + s) * 2 + 1) * 64 + lane];
-            half8 h1 = h0, l1 = l0;
-            if (!SAME) {
-                h1 = b1[((kt * 2 + s) * 2 + 0) * 64 + lane];
-                l1 = b1[((kt * 2 + s) * 2 + 1) * 64 + lane];
-            }
-            // three back-to-back MFMAs per accumulator: a dependent MFMA issued right behind its producer accumulates in
-            // place; alternating the two accumulators made every MFMA wait for the previous write-back (2x slower)
-            MSMP_MFMA_LOLO(2, acc0, w0[kt][s][1], l0);
-            MSMP_MFMA_LOLO(2, acc1, w1[kt][s][1], l1);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(w0[kt][s][1], h0, acc0, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(w0[kt][s][0], l0, acc0, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(w0[kt][s][0], h0, acc0, 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(LEM_SCHED_NOT_MFMA);      // left alone the scheduler alternates acc0 / acc1 when both read the same fragments
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1[kt][s][1], h1, acc1, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1[kt][s][0], l1, acc1, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1[kt][s][0], h1, acc1, 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(LEM_SCHED_NOT_MFMA);
-        }
-}
 
-template <int P, int MODE>
-__global__ __launch_bounds__(512) void lem_encoder_ws_kernel(LemWsArgs a) {
-    constexpr int NS = (P + 1) / 2, M = (3 * P + 2 + 15) / 16;
-    // y fragments [buffer 2][tile 2] | z fragments [tile 2] (16 KB each) | scaled biases [512 + 256]
-    __shared__ __attribute__((aligned(16))) float lds[6 * SPLIT_CHUNK_FLOATS + 768];
-    __shared__ __attribute__((aligned(16))) float xconst[64 * 8];
-    half8* const yfr = reinterpret_cast<half8*>(lds);
-    half8* const zfr = yfr + 4 * LEM_WS_FR;
-    float* const bias_l = lds + 6 * SPLIT_CHUNK_FLOATS;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int ks = wave & 3, role = wave >> 2;
-    const int c = lane & 31, hh = lane >> 5;
-    const long n0 = (long)blockIdx.x * 64;
-    const float LOG2E = 1.44269504088896340736f;
-    const float inv_w = a.scales[4], inv_z = a.scales[5];
-
-    // prologue: zero y(0) of both tiles (buffer 0), stage the biases, load this wave's stationary weights
-    {
-        half8 zero;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) zero[j] = (_Float16)0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) yfr[tid + 512 * i] = zero;
-        bias_l[tid] = a.bias_s[tid];
-        if (tid < 256) bias_l[512 + tid] = a.mlpb_s[tid];
-        if (MODE != 0 && tid < 64) {        // per-node constants of the 64 nodes: [pos_x, (u_t), variables] / [pos_x, (u_t, u_tw+t), pos_t, variables[1:]]
-            const long nn = n0 + tid < a.n_nodes ? n0 + tid : a.n_nodes - 1;
-            float* row = xconst + 8 * tid;
-#pragma unroll
-            for (int f = 0; f < 8; ++f) row[f] = 0.f;
-            row[0] = a.pos_x[nn];
-            if (MODE == 1) {
-                for (int f = 0; f < a.nv; ++f) row[2 + f] = a.vars[(size_t)nn * a.nv + f];
-            } else {
-                row[3] = a.pos_t[nn];
-                for (int f = 1; f < a.nv; ++f) row[3 + f] = a.vars[(size_t)nn * a.nv + f];
-            }
-        }
-    }
-    half8 w[2][4][2][2];
-    half8 wxh[2][M];
-    {
-        const half8* rs = reinterpret_cast<const half8*>(a.rec_s);
-        const half8* wh = reinterpret_cast<const half8*>(a.wx_h);
-#pragma unroll
-        for (int gi = 0; gi < 2; ++gi) {
-            const int grp = 2 * role + gi;
-#pragma unroll
-            for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-                for (int s = 0; s < 2; ++s)
-#pragma unroll
-                    for (int pl = 0; pl < 2; ++pl)
-                        w[gi][kt][s][pl] = rs[(size_t)(grp * 4 + kt) * 1024 + ((s * 4 + ks) * 2 + pl) * 64 + lane];
-#pragma unroll
-            for (int m = 0; m < M; ++m) wxh[gi][m] = wh[((grp * 4 + ks) * 2 + m) * 64 + lane];
-        }
-    }
-    // exponent constants: gate 0 is the sigmoid gate (W scale); gate 1 the tanh candidate (role A: W, role B: Wz)
-    const float c0 = -inv_w * LOG2E, c1 = -2.0f * (role ? inv_z : inv_w) * LOG2E, idt = 1.0f / a.dt;
-    const LemActConst kc{f32x2{c0, c0}, f32x2{c1, c1}, f32x2{idt, idt}, f32x2{1.0f, 1.0f}};
-
-    f32x16 st[2];
-#pragma unroll
-    for (int X = 0; X < 2; ++X)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) st[X][r] = 0.f;
-
-    long node[2];
-#pragma unroll
-    for (int X = 0; X < 2; ++X) {
-        const long n = n0 + 32 * X + c;
-        node[X] = n < a.n_nodes ? n : a.n_nodes - 1;
-    }
-    float xn[2 * NS];
-    __syncthreads();                    // the constants table is read below
-    lem_ws_load_x<P, MODE>(a, xconst + 8 * c, node[0], 0, xn);
-    __syncthreads();
-    if (role) __syncthreads();          // role B runs one stage behind role A
-
-    for (int t = 0; t < a.t_len; ++t) {
-#pragma unroll
-        for (int X = 0; X < 2; ++X) {
-            half8 bx[M];
-            lem_ws_slots<P>(xn, hh, bx);
-            {   // prefetch the inputs of this wave's next work item: (tile 1, t) or (tile 0, t + 1)
-                const int tn = X ? (t + 1 < a.t_len ? t + 1 : t) : t;
-                lem_ws_load_x<P, MODE>(a, xconst + 8 * (32 * (X ^ 1) + c), node[X ^ 1], tn, xn);
-            }
-            // bias + input columns from a zero accumulator input (the bias rides in two K slots paired with 1.0)
-            const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            f32x16 acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wxh[0][0], bx[0], zero, 0, 0, 0);
-            f32x16 acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wxh[1][0], bx[0], zero, 0, 0, 0);
-#pragma unroll
-            for (int m = 1; m < M; ++m) {
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wxh[0][m], bx[m], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wxh[1][m], bx[m], acc1, 0, 0, 0);
-            }
-            const half8* yb = yfr + ((t & 1) * 2 + X) * LEM_WS_FR;
-            if (role) lem_ws_gemm2<false>(w[0], w[1], yb, zfr + X * LEM_WS_FR, lane, acc0, acc1);
-            else lem_ws_gemm2<true>(w[0], w[1], yb, yb, lane, acc0, acc1);
-            lem_ws_update_publish(acc0, acc1, kc, st[X], role ? yfr + (((t + 1) & 1) * 2 + X) * LEM_WS_FR : zfr + X * LEM_WS_FR, ks, lane);
-            __syncthreads();
-        }
-    }
-    if (!role) __syncthreads();         // role A's idle last stage
-    // here: y_X(T) of both tiles is published in buffer T & 1; role-B waves hold their y slices in st[]
-
-    const int X = role;                 // lemoutput_mlp: role A takes tile 0, role B tile 1
-    f32x16 res;
-    if (a.with_mlp) {
-        const half8* ms = reinterpret_cast<const half8*>(a.mlp_s);
-#pragma unroll
-        for (int gi = 0; gi < 2; ++gi)
-#pragma unroll
-            for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-                for (int s = 0; s < 2; ++s)
-#pragma unroll
-                    for (int pl = 0; pl < 2; ++pl)
-                        w[gi][kt][s][pl] = ms[(size_t)(gi * 4 + kt) * 1024 + ((s * 4 + ks) * 2 + pl) * 64 + lane];
-        const float invA = a.scales[6], invB = a.scales[7];
-        const half8* yb = yfr + ((a.t_len & 1) * 2 + X) * LEM_WS_FR;
-        half8* hb = zfr + X * LEM_WS_FR;
-        f32x16 acc;
-        lem_ws_bias(bias_l + 512 + 32 * ks, hh, acc);
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const half8 h0 = yb[((kt * 2 + s) * 2 + 0) * 64 + lane], l0 = yb[((kt * 2 + s) * 2 + 1) * 64 + lane];
-                MSMP_MFMA_LOLO(2, acc, w[0][kt][s][1], l0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[0][kt][s][1], h0, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[0][kt][s][0], l0, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[0][kt][s][0], h0, acc, 0, 0, 0);
-            }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = swishf(acc[r] * invA);
-        lem_ws_publish(acc, hb, ks, lane);
-        __syncthreads();
-        lem_ws_bias(bias_l + 512 + H + 32 * ks, hh, res);
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const half8 h0 = hb[((kt * 2 + s) * 2 + 0) * 64 + lane], l0 = hb[((kt * 2 + s) * 2 + 1) * 64 + lane];
-                MSMP_MFMA_LOLO(2, res, w[1][kt][s][1], l0);
-                res = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[1][kt][s][1], h0, res, 0, 0, 0);
-                res = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[1][kt][s][0], l0, res, 0, 0, 0);
-                res = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[1][kt][s][0], h0, res, 0, 0, 0);
-            }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) res[r] = swishf(res[r] * invB);
-    } else {
-        // y itself: the role-B wave of slice ks holds both tiles; it hands tile 0 to its role-A partner through LDS
-        if (role) *reinterpret_cast<f32x16*>(lds + (size_t)(ks * 64 + lane) * 16) = st[0];
-        __syncthreads();
-        if (role) res = st[1];
-        else res = *reinterpret_cast<const f32x16*>(lds + (size_t)(ks * 64 + lane) * 16);
-    }
-    const long n = n0 + 32 * X + c;
-    if (n < a.n_nodes) {
-        float* o = a.out + (size_t)n * H + 32 * ks + 4 * hh;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            f32x4 v;
-#pragma unroll
-            for (int m = 0; m < 4; ++m) v[m] = res[4 * q + m];
-            *reinterpret_cast<f32x4*>(o + 8 * q) = v;
-        }
-    }
-}
-
-// ----------------------------------------------------------------------------------------------
-// WEIGHT-STATIONARY, ANTI-PHASED edition (default since round 3; msmp_tune("lem", 4)).  Same roles, registers and LDS traffic as
-// lem_encoder_ws_kernel, but a workgroup carries THREE node tiles (96 nodes) and every work item is cut into its matrix half M
-// (input MFMAs + the two gate GEMMs: 50 MFMAs, accumulators kept in registers) and its vector half V (state update + publish),
-// one barrier per half.  The two waves of a SIMD are wave (ks, A) and wave (ks, B); in the two-tile pipeline both ran their
-// GEMMs right after the stage's barrier and their activations afterwards -- matrix beside matrix, vector beside vector on
-// every SIMD: 6.7 k cycles per stage for 3.2 k cycles of matrix work (rocprofv3 SQ counters, profiles/r03c_*).  Here, per time
-// step t and slot j = 0..5:
-//     role A:  M(0,t)    V(0,t)     M(1,t)     V(1,t)   M(2,t)   V(2,t)
-//     role B:  V(1,t-1)  M(2,t-1)   V(2,t-1)   M(0,t)   V(0,t)   M(1,t)
-// so one wave of every SIMD is in a matrix half while the other is in a vector half.  Dependencies (A's V(X,t) publishes
-// z_X(t+1), read by B's M(X,t); B's V(X,t) publishes y_X(t+1), read by A's M(X,t+1) and B's M(X,t+1)) are each separated by
-// at least one barrier, and every buffer's last reader precedes its next writer by a barrier, so y needs ONE buffer per tile.
-// ----------------------------------------------------------------------------------------------
 #if MSMP_PROF_LEM
 __device__ unsigned long long g_prof_lem[16];
 #define LPROF_DECL unsigned lp_m = 0, lp_v = 0, lp_b = 0, lp_w = 0, lp_t = (unsigned)__builtin_readcyclecounter();
@@ -752,9 +480,10 @@ __device__ unsigned long long g_prof_lem[16];
 #endif
 #define LEM_SYNC() do { LPROF(lp_w); __syncthreads(); LPROF(lp_b); } while (0)
 
-// lem_ws_gemm2 with every fragment address formed as  byte base (a __shared__ array)  +  ONE opaque per-lane register  +  a
-// compile-time offset that fits ds_read's 16-bit field: left to itself the compiler hoists the ~100 distinct fragment addresses of
-// the unrolled time step out of the loop as invariants and spills them (scratch reloads with vmcnt(0) waits between the MFMAs).
+// acc0 += W0 B0, acc1 += W1 B1 over K = 128 (B0 / B1: published fragment areas; SAME: one area for both).  Every fragment address is
+// formed as  byte base (a __shared__ array)  +  ONE opaque per-lane register  +  a compile-time offset that fits ds_read's 16-bit
+// field: left to itself the compiler hoists the ~100 distinct fragment addresses of the unrolled time step out of the loop as
+// invariants and spills them (scratch reloads with vmcnt(0) waits between the MFMAs).
 template <bool SAME, int OFF0, int OFF1>
 __device__ __forceinline__ void lem_ws3_gemm2(const half8 (&w0)[4][2][2], const half8 (&w1)[4][2][2], const char* b0, const char* b1,
                                               f32x16& acc0, f32x16& acc1) {
@@ -804,12 +533,14 @@ __device__ __forceinline__ void lem_ws3_gemm2(const half8 (&w0)[4][2][2], const 
                 h1 = *reinterpret_cast<const half8*>(b1 + OFF1 + f * FB);
                 l1 = *reinterpret_cast<const half8*>(b1 + OFF1 + (f + 1) * FB);
             }
+            // three back-to-back MFMAs per accumulator: a dependent MFMA issued right behind its producer accumulates in
+            // place; alternating the two accumulators made every MFMA wait for the previous write-back (2x slower)
             MSMP_MFMA_LOLO(2, acc0, w0[kt][s][1], l0);
             MSMP_MFMA_LOLO(2, acc1, w1[kt][s][1], l1);
             acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(w0[kt][s][1], h0, acc0, 0, 0, 0);
             acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(w0[kt][s][0], l0, acc0, 0, 0, 0);
             acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(w0[kt][s][0], h0, acc0, 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(LEM_SCHED_NOT_MFMA);
+            __builtin_amdgcn_sched_barrier(LEM_SCHED_NOT_MFMA);      // left alone the scheduler alternates acc0 / acc1 when both read the same fragments
             acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1[kt][s][1], h1, acc1, 0, 0, 0);
             acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1[kt][s][0], l1, acc1, 0, 0, 0);
             acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1[kt][s][0], h1, acc1, 0, 0, 0);
@@ -887,8 +618,8 @@ __global__ __launch_bounds__(512) void lem_encoder_ws3_kernel(LemWsArgs a) {
             for (int m = 0; m < M; ++m) wxw[(gi * M + m) * 64] = wh[((grp * 4 + ks) * 2 + m) * 64 + lane];
         }
     }
+    // exponent constants of the state update: gate 0 is the sigmoid gate (W scale); gate 1 the tanh candidate (role A: W, role B: Wz)
     const float c0 = -inv_w * LOG2E, c1 = -2.0f * (role ? inv_z : inv_w) * LOG2E, idt = 1.0f / a.dt;
-    const LemActConst kc{f32x2{c0, c0}, f32x2{c1, c1}, f32x2{idt, idt}, f32x2{1.0f, 1.0f}};
 
     f32x16 st[3];
 #pragma unroll
@@ -970,7 +701,7 @@ __global__ __launch_bounds__(512) void lem_encoder_ws3_kernel(LemWsArgs a) {
     };
     auto half_v = [&](auto Xc) {
         constexpr int X = decltype(Xc)::value;
-        lem_ws_update_publish_q(acc0, acc1, kc, st[X], (role ? yfr : zfr) + X * LEM_WS_FR, ks, lane);
+        lem_ws_update_publish_q(acc0, acc1, c0, c1, idt, st[X], (role ? yfr : zfr) + X * LEM_WS_FR, ks, lane);
     };
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
@@ -1114,380 +845,6 @@ __global__ __launch_bounds__(512) void lem_encoder_ws3_kernel(LemWsArgs a) {
     }
 }
 
-// ----------------------------------------------------------------------------------------------
-// WEIGHT-STATIONARY, ONE WAVE PER SIMD edition (round 4; msmp_tune("lem", 5)).  The issue-port measurements of round 3
-// (scripts/micro/mfma_valu_overlap.hip) say what overlaps on a SIMD: a wave's OWN vector instructions issued between its MFMAs are
-// free, vector and matrix work of DIFFERENT waves add up.  The anti-phased kernel above pairs a matrix half of one wave with a
-// vector half of the other wave of the SIMD -- the sum, 2 150-2 400 clocks per slot for 1 600 clocks of MFMAs.  Here a workgroup
-// is FOUR waves, one per SIMD, with the whole register file each (512 registers: all four gate blocks of the wave's 32 channels,
-// 256 registers of stationary weights, live in it), every wave plays both roles for its channel slice, and a wave's matrix work of
-// one node tile is interleaved IN PROGRAM ORDER with its vector work of the other tile.  Two tiles (64 nodes) per workgroup, four
-// fused phases per time step, one barrier per phase:
-//     phase 0:  M_A(0,t)  ||  V_B(1,t-1)        M_A(X,t): g2, g3 of tile X from y_X(t)            (50 MFMAs)
-//     phase 1:  M_A(1,t)  ||  V_A(0,t)          V_A(X,t): z_X <- z + dt s(g2)(tanh(g3) - z), published as hi/lo fragments
-//     phase 2:  M_B(0,t)  ||  V_A(1,t)          M_B(X,t): g1 from y_X(t), lin from z_X(t+1)       (50 MFMAs)
-//     phase 3:  M_B(1,t)  ||  V_B(0,t)          V_B(X,t): y_X <- y + dt s(g1)(tanh(lin) - y), published
-// Every fragment area's last reader precedes its next writer by a barrier (y_0: read in phases 0 and 2, written in 3; y_1: read
-// in 1 and 3, written in 0; z_0: read in 2, written in 1; z_1: read in 3, written in 2), so one buffer per tile and state.
-// The chain M_A -> V_A -> M_B -> V_B of a tile is four phases, two tiles offset by one phase keep the matrix pipe fed in every
-// phase: 4 x 50 MFMAs per step and wave = the MFMA-bound 6.4 k clocks if the vector work hides (264 issue slots of the ~300 behind
-// 50 MFMAs).  Same per-value arithmetic as the other weight-stationary editions: a tile's result does not depend on the edition.
-// ----------------------------------------------------------------------------------------------
-// acc += W B with the stationary weight fragment read STRAIGHT from the accumulation registers (AGPRs): the 256 registers of weights
-// live there for the whole kernel, the 256 architectural registers hold states, accumulators and the vector work.  (Left to the
-// register allocator the weights end up in AGPRs as SPILL slots: four v_accvgpr_read per fragment in front of every MFMA.)
-// Inline asm is invisible to the hazard recogniser: B comes from LDS reads (waited for by the compiler), acc is read by vector
-// instructions only a whole phase (and a barrier) later, and a B-fragment register is next written by an LDS read issued at least one
-// K group (six MFMAs) after the MFMA that read it.  (A queued dependent MFMA reads its A / B operands when it STARTS, tens of clocks
-// after it issued: round 4 measured run-to-run differences of 1e-1 in the node tail when an inline-asm split overwrote B registers two
-// instructions behind the MFMAs that read them.  This edition is opt-in -- msmp_tune("lem", 5) -- and checked bit for bit against the
-// default edition in tests/test_gpu_kernels.py; the default edition's MFMAs are compiler builtins.)
-__device__ __forceinline__ void mfma_aw(f32x16& acc, const half8& w_agpr, const half8& b) {
-    asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "a"(w_agpr), "v"(b));
-}
-// One value pair (r, r + 1) of a state update st <- st + dt s(a0) (tanh(a1) - st), cut into SIX pieces of 3-6 instructions, one
-// behind each MFMA of a K group (a dependent vector instruction issues ~8 clocks after its producer, a transcendental later still:
-// every piece only consumes what the previous piece -- a whole MFMA earlier -- produced).  Same operations in the same order as
-// lem_ws_update_publish_q: the same bits.
-struct LemPairTmp {
-    float ta[2], tb[2], ea[2], eb[2], qb[2], m[2], rr[2], d[2];
-    f32x2 sv;
-};
-template <int PIECE>
-__device__ __forceinline__ void lem_ws1_piece(const f32x16& a0, const f32x16& a1, int r, float c0, float c1, float idt, f32x16& st,
-                                              LemPairTmp& p, half8& phi, half8& plo, int j) {
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-        if (PIECE == 0) {
-            p.ta[e] = a0[r + e] * c0;
-            p.tb[e] = vmin(a1[r + e] * c1, 60.f);
-        } else if (PIECE == 1) {
-            p.ea[e] = msmp_exp2(p.ta[e]);
-            p.eb[e] = msmp_exp2(p.tb[e]);
-        } else if (PIECE == 2) {
-            p.qb[e] = p.eb[e] + 1.0f;
-            p.m[e] = __builtin_fmaf(p.ea[e], idt, idt) * p.qb[e];
-        } else if (PIECE == 3) {
-            p.rr[e] = msmp_rcp(p.m[e]);
-            p.d[e] = 1.0f - p.eb[e];
-        } else if (PIECE == 4) {
-            p.sv[e] = __builtin_fmaf(p.rr[e], __builtin_fmaf(-st[r + e], p.qb[e], p.d[e]), st[r + e]);
-            st[r + e] = p.sv[e];
-        }
-    }
-    if (PIECE == 5) {
-        const half2 hp = __builtin_convertvector(p.sv, half2);
-        const half2 lp = split_lo_pair(hp, p.sv);
-        phi[j] = hp[0];
-        phi[j + 1] = hp[1];
-        plo[j] = lp[0];
-        plo[j + 1] = lp[1];
-    }
-}
-
-// One fused phase: (o0, o1) = input MFMAs + the two gate GEMMs over K = 128 of one tile;  beside them, when DO_V, the state update of
-// ANOTHER tile from (i0, i1) -- accumulators a previous phase produced -- and its publication.  Eight K groups of 6 MFMAs; behind
-// EVERY MFMA one piece of the group's value pair, pinned there with scheduling barriers (left alone the scheduler gathers the
-// vector instructions in front of three back-to-back MFMAs: measured 2.9 k clocks per phase instead of the MFMAs' 1.6 k).
-template <bool SAME, bool DO_V, int M>
-__device__ __forceinline__ void lem_ws1_phase(const half8 (&w0)[4][2][2], const half8 (&w1)[4][2][2], const half8* wx0, const half8* wx1,
-                                              const half8 (&bx)[M], const char* fb0, const char* fb1, f32x16& o0, f32x16& o1,
-                                              const f32x16& i0, const f32x16& i1, float c0, float c1, float idt, f32x16& st, char* pub) {
-    constexpr int FB = 64 * 16;       // bytes of one fragment plane
-    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    half8 h0 = *reinterpret_cast<const half8*>(fb0), l0 = *reinterpret_cast<const half8*>(fb0 + FB);
-    half8 h1 = h0, l1 = l0;
-    if (!SAME) {
-        h1 = *reinterpret_cast<const half8*>(fb1);
-        l1 = *reinterpret_cast<const half8*>(fb1 + FB);
-    }
-    o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wx0[0], bx[0], zero, 0, 0, 0);
-    o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wx1[0], bx[0], zero, 0, 0, 0);
-#pragma unroll
-    for (int m = 1; m < M; ++m) {
-        o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wx0[m * 64], bx[m], o0, 0, 0, 0);
-        o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wx1[m * 64], bx[m], o1, 0, 0, 0);
-    }
-    half8 phi, plo;
-#pragma unroll
-    for (int g = 0; g < 8; ++g) {
-        const int kt = g >> 1, s = g & 1;
-        const int r = 2 * g, j = 2 * (g & 3);      // the value pair (r, r + 1) of the update: half g >> 2, elements j, j + 1
-        LemPairTmp tmp;
-        half8 nh0 = h0, nl0 = l0, nh1 = h1, nl1 = l1;
-        __builtin_amdgcn_sched_barrier(0);
-        // The two accumulators ALTERNATE: a dependent MFMA that is not issued right behind its producer waits for the producer's
-        // write-back (~64 clocks after issue: the anti-phased kernel measured 2x for alternating accumulators with nothing between
-        // them; with one vector piece between the MFMAs the dependent one is two MFMAs and two pieces behind -- nothing waits, and
-        // each chain still accumulates in its own order (w_lo h, w_hi l, w_hi h per K group): the same bits).
-        if (MSMP_LOLO >= 2) { mfma_aw(o0, w0[kt][s][1], l0); mfma_aw(o1, w1[kt][s][1], l1); }
-        mfma_aw(o0, w0[kt][s][1], h0);
-        if (g < 7) {                                // next group's fragments: requested behind this group's first MFMA
-            const int f = (g + 1) * 2;
-            nh0 = *reinterpret_cast<const half8*>(fb0 + f * FB);
-            nl0 = *reinterpret_cast<const half8*>(fb0 + (f + 1) * FB);
-            if (!SAME) {
-                nh1 = *reinterpret_cast<const half8*>(fb1 + f * FB);
-                nl1 = *reinterpret_cast<const half8*>(fb1 + (f + 1) * FB);
-            }
-        }
-        if (DO_V) lem_ws1_piece<0>(i0, i1, r, c0, c1, idt, st, tmp, phi, plo, j);
-        __builtin_amdgcn_sched_barrier(0);
-        mfma_aw(o1, w1[kt][s][1], h1);
-        if (DO_V) lem_ws1_piece<1>(i0, i1, r, c0, c1, idt, st, tmp, phi, plo, j);
-        __builtin_amdgcn_sched_barrier(0);
-        mfma_aw(o0, w0[kt][s][0], l0);
-        if (DO_V) lem_ws1_piece<2>(i0, i1, r, c0, c1, idt, st, tmp, phi, plo, j);
-        __builtin_amdgcn_sched_barrier(0);
-        mfma_aw(o1, w1[kt][s][0], l1);
-        if (DO_V) lem_ws1_piece<3>(i0, i1, r, c0, c1, idt, st, tmp, phi, plo, j);
-        __builtin_amdgcn_sched_barrier(0);
-        mfma_aw(o0, w0[kt][s][0], h0);
-        if (DO_V) lem_ws1_piece<4>(i0, i1, r, c0, c1, idt, st, tmp, phi, plo, j);
-        __builtin_amdgcn_sched_barrier(0);
-        mfma_aw(o1, w1[kt][s][0], h1);
-        if (DO_V) {
-            lem_ws1_piece<5>(i0, i1, r, c0, c1, idt, st, tmp, phi, plo, j);
-            if ((g & 3) == 3) {                     // a half tile (8 values) is complete: publish its hi / lo fragments
-                const int sv = g >> 2;
-                *reinterpret_cast<half8*>(pub + (sv * 2 + 0) * FB) = phi;
-                *reinterpret_cast<half8*>(pub + (sv * 2 + 1) * FB) = plo;
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        h0 = nh0; l0 = nl0;
-        if (SAME) { h1 = nh0; l1 = nl0; } else { h1 = nh1; l1 = nl1; }
-    }
-}
-
-template <int P, int MODE>
-__global__ __launch_bounds__(256, 1) void lem_encoder_ws1_kernel(LemWsArgs a) {
-    constexpr int NS = (P + 1) / 2, M = (3 * P + 2 + 15) / 16;
-    // y fragments [tile 2] | z fragments [tile 2] (16 KB each) | scaled biases [512 + 256]
-    __shared__ __attribute__((aligned(16))) float lds[4 * SPLIT_CHUNK_FLOATS + 768];
-    __shared__ __attribute__((aligned(16))) float xconst[64 * 8];
-    __shared__ half8 wxl[4 * 4 * M * 64];               // input-column fragments: [wave 4][gate 4][m M][lane 64]
-    half8* const yfr = reinterpret_cast<half8*>(lds);
-    half8* const zfr = yfr + 2 * LEM_WS_FR;
-    float* const bias_l = lds + 4 * SPLIT_CHUNK_FLOATS;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int ks = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int c = lane & 31, hh = lane >> 5;
-    const long n0 = (long)blockIdx.x * 64;
-    const bool two = n0 + 32 < a.n_nodes;              // (uniform) the second tile holds nodes
-    const float LOG2E = 1.44269504088896340736f;
-    const float inv_w = a.scales[4], inv_z = a.scales[5];
-    const int T = a.t_len;
-
-    {   // prologue: y(0) = 0 for both tiles, biases, per-node constants
-        half8 zero;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) zero[j] = (_Float16)0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) yfr[tid + 256 * i] = zero;
-        bias_l[tid] = a.bias_s[tid];
-        bias_l[256 + tid] = a.bias_s[256 + tid];
-        bias_l[512 + tid] = a.mlpb_s[tid];
-        if (MODE != 0 && tid < 64) {
-            const long nn = n0 + tid < a.n_nodes ? n0 + tid : a.n_nodes - 1;
-            float* row = xconst + 8 * tid;
-#pragma unroll
-            for (int f = 0; f < 8; ++f) row[f] = 0.f;
-            row[0] = a.pos_x[nn];
-            if (MODE == 1) {
-                for (int f = 0; f < a.nv; ++f) row[2 + f] = a.vars[(size_t)nn * a.nv + f];
-            } else {
-                row[3] = a.pos_t[nn];
-                for (int f = 1; f < a.nv; ++f) row[3 + f] = a.vars[(size_t)nn * a.nv + f];
-            }
-        }
-    }
-    // stationary weights: the four gate blocks (rec_s order: g2, g3 | g1, lin) of this wave's 32 rows
-    half8 w[4][4][2][2];
-    half8* const wxw = wxl + (size_t)ks * (4 * M * 64) + lane;        // this wave's: [gate 4][m M][lane 64]
-    {
-        const half8* rs = reinterpret_cast<const half8*>(a.rec_s);
-        const half8* wh = reinterpret_cast<const half8*>(a.wx_h);
-#pragma unroll
-        for (int grp = 0; grp < 4; ++grp) {
-#pragma unroll
-            for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-                for (int s = 0; s < 2; ++s)
-#pragma unroll
-                    for (int pl = 0; pl < 2; ++pl)
-                        w[grp][kt][s][pl] = rs[(size_t)(grp * 4 + kt) * 1024 + ((s * 4 + ks) * 2 + pl) * 64 + lane];
-#pragma unroll
-            for (int m = 0; m < M; ++m) wxw[(grp * M + m) * 64] = wh[((grp * 4 + ks) * 2 + m) * 64 + lane];
-        }
-    }
-    const float c0 = -inv_w * LOG2E, c1a = -2.0f * inv_w * LOG2E, c1b = -2.0f * inv_z * LOG2E, idt = 1.0f / a.dt;
-
-    f32x16 sz[2], sy[2];
-#pragma unroll
-    for (int X = 0; X < 2; ++X)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { sz[X][r] = 0.f; sy[X][r] = 0.f; }
-    // per-lane byte addresses: fragment areas as B operands (read) and this wave's K tile of them (published)
-    constexpr int AREA = LEM_WS_FR * 16;
-    const char* const fy0 = reinterpret_cast<const char*>(yfr) + lane * 16;
-    const char* const fy1 = fy0 + AREA;
-    const char* const fz0 = reinterpret_cast<const char*>(zfr) + lane * 16;
-    const char* const fz1 = fz0 + AREA;
-    char* const py0 = reinterpret_cast<char*>(yfr) + lane * 16 + ks * (4 * 64 * 16);
-    char* const py1 = py0 + AREA;
-    char* const pz0 = reinterpret_cast<char*>(zfr) + lane * 16 + ks * (4 * 64 * 16);
-    char* const pz1 = pz0 + AREA;
-
-    // Step inputs: x_X(t) is requested a phase before its B fragments are formed (the loads fly behind that phase's MFMAs).
-    float xn0[2 * NS], xn1[2 * NS];
-    half8 bx0[M], bx1[M];
-    auto fetch0 = [&](int t) {
-        const long n = n0 + c;
-        lem_ws_load_x<P, MODE>(a, xconst + 8 * c, n < a.n_nodes ? n : a.n_nodes - 1, t, xn0);
-    };
-    auto fetch1 = [&](int t) {
-        const long n = n0 + 32 + c;
-        lem_ws_load_x<P, MODE>(a, xconst + 8 * (32 + c), n < a.n_nodes ? n : a.n_nodes - 1, t, xn1);
-    };
-    f32x16 a0, a1, b0, b1, c0a, c1acc, d0, d1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { a0[r] = a1[r] = b0[r] = b1[r] = c0a[r] = c1acc[r] = d0[r] = d1[r] = 0.f; }
-    __syncthreads();                    // the constants table and y(0) are read below
-    fetch0(0);
-    fetch1(0);
-    lem_ws_slots<P>(xn0, hh, bx0);
-    lem_ws_slots<P>(xn1, hh, bx1);
-
-    const int role = 0;
-    (void)role;
-    LPROF_DECL
-    for (int t = 0; t < T; ++t) {
-        const int tn = t + 1 < T ? t + 1 : t;
-        // phase 0: M_A(0,t) || V_B(1,t-1)  (nothing to update before the first step)
-        if (t == 0) lem_ws1_phase<true, false, M>(w[0], w[1], wxw, wxw + M * 64, bx0, fy0, fy0, a0, a1, d0, d1, c0, c1b, idt, sy[1], py1);
-        else lem_ws1_phase<true, true, M>(w[0], w[1], wxw, wxw + M * 64, bx0, fy0, fy0, a0, a1, d0, d1, c0, c1b, idt, sy[1], py1);
-        LPROF(lp_m);
-        LEM_SYNC();
-        // phase 1: M_A(1,t) || V_A(0,t)
-        lem_ws1_phase<true, true, M>(w[0], w[1], wxw, wxw + M * 64, bx1, fy1, fy1, b0, b1, a0, a1, c0, c1a, idt, sz[0], pz0);
-        LPROF(lp_m);
-        LEM_SYNC();
-        // phase 2: M_B(0,t) || V_A(1,t); x_0(t+1) requested, its fragments formed behind the phase (the last use of x_0(t) is this phase's)
-        fetch0(tn);
-        lem_ws1_phase<false, true, M>(w[2], w[3], wxw + 2 * M * 64, wxw + 3 * M * 64, bx0, fy0, fz0, c0a, c1acc, b0, b1, c0, c1a, idt, sz[1], pz1);
-        LPROF(lp_m);
-        lem_ws_slots<P>(xn0, hh, bx0);
-        LPROF(lp_v);
-        LEM_SYNC();
-        // phase 3: M_B(1,t) || V_B(0,t); x_1(t+1) likewise
-        fetch1(tn);
-        lem_ws1_phase<false, true, M>(w[2], w[3], wxw + 2 * M * 64, wxw + 3 * M * 64, bx1, fy1, fz1, d0, d1, c0a, c1acc, c0, c1b, idt, sy[0], py0);
-        LPROF(lp_m);
-        lem_ws_slots<P>(xn1, hh, bx1);
-        LPROF(lp_v);
-        LEM_SYNC();
-    }
-    LPROF_FLUSH
-    {   // V_B(1, T-1): the last update of tile 1
-        half8 phi, plo;
-#pragma unroll
-        for (int g = 0; g < 8; ++g) {
-            LemPairTmp tmp;
-            lem_ws1_piece<0>(d0, d1, 2 * g, c0, c1b, idt, sy[1], tmp, phi, plo, 2 * (g & 3));
-            lem_ws1_piece<1>(d0, d1, 2 * g, c0, c1b, idt, sy[1], tmp, phi, plo, 2 * (g & 3));
-            lem_ws1_piece<2>(d0, d1, 2 * g, c0, c1b, idt, sy[1], tmp, phi, plo, 2 * (g & 3));
-            lem_ws1_piece<3>(d0, d1, 2 * g, c0, c1b, idt, sy[1], tmp, phi, plo, 2 * (g & 3));
-            lem_ws1_piece<4>(d0, d1, 2 * g, c0, c1b, idt, sy[1], tmp, phi, plo, 2 * (g & 3));
-            lem_ws1_piece<5>(d0, d1, 2 * g, c0, c1b, idt, sy[1], tmp, phi, plo, 2 * (g & 3));
-            if ((g & 3) == 3) {
-                *reinterpret_cast<half8*>(py1 + ((g >> 2) * 2 + 0) * 1024) = phi;
-                *reinterpret_cast<half8*>(py1 + ((g >> 2) * 2 + 1) * 1024) = plo;
-            }
-        }
-    }
-    __syncthreads();
-    // here: y_X(T) of both tiles is published in yfr; every wave holds its y slices in sy[]
-
-    if (a.with_mlp) {
-        const half8* ms = reinterpret_cast<const half8*>(a.mlp_s);
-#pragma unroll
-        for (int gi = 0; gi < 2; ++gi)
-#pragma unroll
-            for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-                for (int s = 0; s < 2; ++s)
-#pragma unroll
-                    for (int pl = 0; pl < 2; ++pl)
-                        w[gi][kt][s][pl] = ms[(size_t)(gi * 4 + kt) * 1024 + ((s * 4 + ks) * 2 + pl) * 64 + lane];
-        const float invA = a.scales[6], invB = a.scales[7];
-        // lemoutput_mlp on both tiles: Swish(Wa y + ba) published into the (dead) z areas, then Swish(Wb . + bb)
-#pragma unroll
-        for (int X = 0; X < 2; ++X) {
-            const half8* yb = yfr + X * LEM_WS_FR;
-            f32x16 acc;
-            lem_ws_bias(bias_l + 512 + 32 * ks, hh, acc);
-#pragma unroll
-            for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    const half8 h0 = yb[((kt * 2 + s) * 2 + 0) * 64 + lane], l0 = yb[((kt * 2 + s) * 2 + 1) * 64 + lane];
-                    MSMP_MFMA_LOLO(2, acc, w[0][kt][s][1], l0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[0][kt][s][1], h0, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[0][kt][s][0], l0, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[0][kt][s][0], h0, acc, 0, 0, 0);
-                }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = swishf(acc[r] * invA);
-            lem_ws_publish(acc, zfr + X * LEM_WS_FR, ks, lane);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int X = 0; X < 2; ++X) {
-            const half8* hb = zfr + X * LEM_WS_FR;
-            f32x16 res;
-            lem_ws_bias(bias_l + 512 + H + 32 * ks, hh, res);
-#pragma unroll
-            for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    const half8 h0 = hb[((kt * 2 + s) * 2 + 0) * 64 + lane], l0 = hb[((kt * 2 + s) * 2 + 1) * 64 + lane];
-                    MSMP_MFMA_LOLO(2, res, w[1][kt][s][1], l0);
-                    res = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[1][kt][s][1], h0, res, 0, 0, 0);
-                    res = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[1][kt][s][0], l0, res, 0, 0, 0);
-                    res = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[1][kt][s][0], h0, res, 0, 0, 0);
-                }
-            const long n = n0 + 32 * X + c;
-            if (n < a.n_nodes) {
-                float* o = a.out + (size_t)n * H + 32 * ks + 4 * hh;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    f32x4 v;
-#pragma unroll
-                    for (int m = 0; m < 4; ++m) v[m] = swishf(res[4 * q + m] * invB);
-                    *reinterpret_cast<f32x4*>(o + 8 * q) = v;
-                }
-            }
-        }
-    } else {
-#pragma unroll
-        for (int X = 0; X < 2; ++X) {
-            const long n = n0 + 32 * X + c;
-            if (n < a.n_nodes) {
-                float* o = a.out + (size_t)n * H + 32 * ks + 4 * hh;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    f32x4 v;
-#pragma unroll
-                    for (int m = 0; m < 4; ++m) v[m] = sy[X][4 * q + m];
-                    *reinterpret_cast<f32x4*>(o + 8 * q) = v;
-                }
-            }
-        }
-    }
-    (void)two;
-}
-
 // fp32 chunks [128 out][32 k] (row-major, as `rec`) -> bf16x3 A fragments, acc order: thread = (chunk, s, T, lane)
 __global__ __launch_bounds__(256) void pack_lem_b3_kernel(const float* __restrict__ chunks, int n_chunks, float* __restrict__ out) {
     const int id = blockIdx.x * 256 + threadIdx.x;
@@ -1546,9 +903,6 @@ extern "C" __attribute__((visibility("default"))) int msmp_debug_lem_partition(i
     if (full_out) *full_out = full == 0x7fffffff ? (int64_t)g : full;
     return 0;
 }
-int g_lem_nodes = 1;     // msmp_tune("lem_nodes", 0): msmp_lem_encoder_nodes_f32 declines, callers assemble the [N,T,ninp] tensor (A/B)
-int g_lem_split = 4;     // 4: weight-stationary anti-phased kernel (three node tiles), 3: weight-stationary two-tile kernel (round 2),
-                         // 0: fp32 MFMA (msmp_tune "lem"; "split" 1/0 selects 4/0)
 extern "C" int64_t msmp_packed_lem_floats(void) { return lem_layout().total; }
 
 extern "C" int msmp_pack_lem_f32(const float* weights, const float* weights_lin_z, const float* bias, const float* bias_lin_z,
@@ -1569,70 +923,60 @@ extern "C" int msmp_pack_lem_f32(const float* weights, const float* weights_lin_
 
 extern "C" int msmp_lem_input_stride(int ninp) { return ninp >= 1 && ninp <= LEM_MAX_INP ? 2 * ((ninp + 1) / 2) : -1; }
 
+// the weight-stationary kernel's arguments on the packed blob; the caller sets the step inputs (xin, or the node arrays)
+static LemWsArgs lem_ws_args(const float* packed, int64_t n_nodes, int t_len, int with_mlp, float dt, float* h_out) {
+    const LemLayout L = lem_layout();
+    LemWsArgs a{};
+    a.n_nodes = (long)n_nodes;
+    a.t_len = t_len;
+    a.with_mlp = with_mlp;
+    a.dt = dt;
+    a.rec_s = packed + L.rec_s;
+    a.mlp_s = packed + L.mlp_s;
+    a.bias_s = packed + L.bias_s;
+    a.wx_h = packed + L.wx_h;
+    a.mlpb_s = packed + L.mlpb_s;
+    a.scales = packed + L.scales;
+    a.out = h_out;
+    return a;
+}
+
+// lem_encoder_ws3_kernel<ninp, MODE> over the lem_partition grid.  Instantiated for ninp = P..8 from P = 1 (MODE 0, assembled
+// inputs), 3 (MODE 1, 1-D node arrays) or 4 (MODE 2, 2-D node arrays); an ninp outside that range takes P = 8.
+template <int MODE, int P = MODE == 0 ? 1 : MODE + 2>
+static void lem_ws3_launch(LemWsArgs a, int ninp, hipStream_t st) {
+    if constexpr (P < 8)
+        if (ninp != P) return lem_ws3_launch<MODE, P + 1>(a, ninp, st);
+    const unsigned grid = lem_partition(a.n_nodes, &a.full_wgs);
+    hipLaunchKernelGGL((lem_encoder_ws3_kernel<P, MODE>), dim3(grid), dim3(512), 0, st, a);
+}
+
 extern "C" int msmp_lem_encoder_f32(const float* xin, int64_t n_nodes, int t_len, int ninp, float dt, const float* packed,
                                     int with_mlp, float* h_out, msmp_stream_t stream) {
     MSMP_REQUIRE(xin && packed && h_out, MSMP_ERR_ARG, "msmp_lem_encoder_f32: null pointer");
     MSMP_REQUIRE(n_nodes > 0 && n_nodes < (1L << 31) && t_len >= 1, MSMP_ERR_ARG, "msmp_lem_encoder_f32: bad sizes");
     MSMP_REQUIRE(ninp >= 1 && ninp <= LEM_MAX_INP, MSMP_ERR_UNSUPPORTED, "msmp_lem_encoder_f32: ninp=%d outside 1..%d", ninp, LEM_MAX_INP);
-    const LemLayout L = lem_layout();
-    LemArgs a{xin, (long)n_nodes, t_len, with_mlp, dt, packed + L.rec, packed + L.mlp, packed + L.bias, packed + L.wx,
-              packed + L.mlpb, h_out};
-    const unsigned grid = (unsigned)((n_nodes + 127) / 128);
-    timing_begin(MSMP_K_LEM, (hipStream_t)stream);
-    if (g_lem_split == 5) {
-        LemWsArgs wa{xin, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, (long)n_nodes, t_len, with_mlp, dt, packed + L.rec_s,
-                     packed + L.mlp_s, packed + L.bias_s, packed + L.wx_h, packed + L.mlpb_s, packed + L.scales, h_out};
-        const unsigned g1 = (unsigned)((n_nodes + 63) / 64);
-        hipStream_t st = (hipStream_t)stream;
-        switch (ninp) {
-            case 1: hipLaunchKernelGGL((lem_encoder_ws1_kernel<1, 0>), dim3(g1), dim3(256), 0, st, wa); break;
-            case 2: hipLaunchKernelGGL((lem_encoder_ws1_kernel<2, 0>), dim3(g1), dim3(256), 0, st, wa); break;
-            case 3: hipLaunchKernelGGL((lem_encoder_ws1_kernel<3, 0>), dim3(g1), dim3(256), 0, st, wa); break;
-            case 4: hipLaunchKernelGGL((lem_encoder_ws1_kernel<4, 0>), dim3(g1), dim3(256), 0, st, wa); break;
-            case 5: hipLaunchKernelGGL((lem_encoder_ws1_kernel<5, 0>), dim3(g1), dim3(256), 0, st, wa); break;
-            case 6: hipLaunchKernelGGL((lem_encoder_ws1_kernel<6, 0>), dim3(g1), dim3(256), 0, st, wa); break;
-            case 7: hipLaunchKernelGGL((lem_encoder_ws1_kernel<7, 0>), dim3(g1), dim3(256), 0, st, wa); break;
-            default: hipLaunchKernelGGL((lem_encoder_ws1_kernel<8, 0>), dim3(g1), dim3(256), 0, st, wa); break;
+    const bool split = msmp_tune_get("split") != 0;
+    hipStream_t st = (hipStream_t)stream;
+    timing_begin(MSMP_K_LEM, st);
+    if (split) {                        // fp16-split path: the weight-stationary kernel
+        LemWsArgs wa = lem_ws_args(packed, n_nodes, t_len, with_mlp, dt, h_out);
+        wa.xin = xin;
+        lem_ws3_launch<0>(wa, ninp, st);
+    } else {                            // exact fp32
+        const LemLayout L = lem_layout();
+        LemArgs a{xin, (long)n_nodes, t_len, with_mlp, dt, packed + L.rec, packed + L.mlp, packed + L.bias, packed + L.wx,
+                  packed + L.mlpb, h_out};
+        const unsigned grid = (unsigned)((n_nodes + 127) / 128);
+        switch ((ninp + 1) / 2) {
+            case 1: hipLaunchKernelGGL(lem_encoder_kernel<1>, dim3(grid), dim3(256), 0, st, a); break;
+            case 2: hipLaunchKernelGGL(lem_encoder_kernel<2>, dim3(grid), dim3(256), 0, st, a); break;
+            case 3: hipLaunchKernelGGL(lem_encoder_kernel<3>, dim3(grid), dim3(256), 0, st, a); break;
+            default: hipLaunchKernelGGL(lem_encoder_kernel<4>, dim3(grid), dim3(256), 0, st, a); break;
         }
-    } else if (g_lem_split == 4) {
-        LemWsArgs wa{xin, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, (long)n_nodes, t_len, with_mlp, dt, packed + L.rec_s,
-                     packed + L.mlp_s, packed + L.bias_s, packed + L.wx_h, packed + L.mlpb_s, packed + L.scales, h_out};
-        const unsigned g96 = lem_partition(n_nodes, &wa.full_wgs);
-        hipStream_t st = (hipStream_t)stream;
-        switch (ninp) {
-            case 1: hipLaunchKernelGGL((lem_encoder_ws3_kernel<1, 0>), dim3(g96), dim3(512), 0, st, wa); break;
-            case 2: hipLaunchKernelGGL((lem_encoder_ws3_kernel<2, 0>), dim3(g96), dim3(512), 0, st, wa); break;
-            case 3: hipLaunchKernelGGL((lem_encoder_ws3_kernel<3, 0>), dim3(g96), dim3(512), 0, st, wa); break;
-            case 4: hipLaunchKernelGGL((lem_encoder_ws3_kernel<4, 0>), dim3(g96), dim3(512), 0, st, wa); break;
-            case 5: hipLaunchKernelGGL((lem_encoder_ws3_kernel<5, 0>), dim3(g96), dim3(512), 0, st, wa); break;
-            case 6: hipLaunchKernelGGL((lem_encoder_ws3_kernel<6, 0>), dim3(g96), dim3(512), 0, st, wa); break;
-            case 7: hipLaunchKernelGGL((lem_encoder_ws3_kernel<7, 0>), dim3(g96), dim3(512), 0, st, wa); break;
-            default: hipLaunchKernelGGL((lem_encoder_ws3_kernel<8, 0>), dim3(g96), dim3(512), 0, st, wa); break;
-        }
-    } else if (g_lem_split == 3) {
-        LemWsArgs wa{xin, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, (long)n_nodes, t_len, with_mlp, dt, packed + L.rec_s,
-                     packed + L.mlp_s, packed + L.bias_s, packed + L.wx_h, packed + L.mlpb_s, packed + L.scales, h_out};
-        const unsigned g64 = (unsigned)((n_nodes + 63) / 64);
-        hipStream_t st = (hipStream_t)stream;
-        switch (ninp) {
-            case 1: hipLaunchKernelGGL((lem_encoder_ws_kernel<1, 0>), dim3(g64), dim3(512), 0, st, wa); break;
-            case 2: hipLaunchKernelGGL((lem_encoder_ws_kernel<2, 0>), dim3(g64), dim3(512), 0, st, wa); break;
-            case 3: hipLaunchKernelGGL((lem_encoder_ws_kernel<3, 0>), dim3(g64), dim3(512), 0, st, wa); break;
-            case 4: hipLaunchKernelGGL((lem_encoder_ws_kernel<4, 0>), dim3(g64), dim3(512), 0, st, wa); break;
-            case 5: hipLaunchKernelGGL((lem_encoder_ws_kernel<5, 0>), dim3(g64), dim3(512), 0, st, wa); break;
-            case 6: hipLaunchKernelGGL((lem_encoder_ws_kernel<6, 0>), dim3(g64), dim3(512), 0, st, wa); break;
-            case 7: hipLaunchKernelGGL((lem_encoder_ws_kernel<7, 0>), dim3(g64), dim3(512), 0, st, wa); break;
-            default: hipLaunchKernelGGL((lem_encoder_ws_kernel<8, 0>), dim3(g64), dim3(512), 0, st, wa); break;
-        }
-    } else
-    switch ((ninp + 1) / 2) {
-        case 1: hipLaunchKernelGGL(lem_encoder_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a); break;
-        case 2: hipLaunchKernelGGL(lem_encoder_kernel<2>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a); break;
-        case 3: hipLaunchKernelGGL(lem_encoder_kernel<3>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a); break;
-        default: hipLaunchKernelGGL(lem_encoder_kernel<4>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a); break;
     }
-    timing_end(MSMP_K_LEM, (hipStream_t)stream);
-    return check_launch("lem_encoder_kernel");
+    timing_end(MSMP_K_LEM, st);
+    return check_launch(split ? "lem_encoder_ws3_kernel" : "lem_encoder_kernel");
 }
 
 // The same weight-stationary kernel with the step inputs assembled in the kernel from the node arrays (no [N, T, ninp]
@@ -1646,61 +990,19 @@ extern "C" int msmp_lem_encoder_nodes_f32(const float* u, const float* pos_x, co
     MSMP_REQUIRE(n_nodes > 0 && n_nodes < (1L << 31) && tw >= 1 && nv >= 1, MSMP_ERR_ARG, "msmp_lem_encoder_nodes_f32: bad sizes");
     const int ninp = (two_d ? 3 : 2) + nv;
     MSMP_REQUIRE(ninp <= LEM_MAX_INP, MSMP_ERR_UNSUPPORTED, "msmp_lem_encoder_nodes_f32: ninp=%d > %d", ninp, LEM_MAX_INP);
-    MSMP_REQUIRE((g_lem_split == 3 || g_lem_split == 4 || g_lem_split == 5) && g_lem_nodes, MSMP_ERR_UNSUPPORTED,
-                 "msmp_lem_encoder_nodes_f32: only the weight-stationary editions (msmp_tune lem 3 / 4)");
-    const LemLayout L = lem_layout();
-    LemWsArgs wa{nullptr, u, pos_x, pos_t, vars, dt_cum, tw, nv, (long)n_nodes, tw, with_mlp, dt, packed + L.rec_s, packed + L.mlp_s,
-                 packed + L.bias_s, packed + L.wx_h, packed + L.mlpb_s, packed + L.scales, h_out};
-    const unsigned g64 = (unsigned)((n_nodes + 63) / 64), g96 = g_lem_split == 4 ? lem_partition(n_nodes, &wa.full_wgs) : 0u;
+    MSMP_REQUIRE(msmp_tune_get("split"), MSMP_ERR_UNSUPPORTED, "msmp_lem_encoder_nodes_f32: only on the fp16-split path (weight-stationary kernel)");
+    LemWsArgs wa = lem_ws_args(packed, n_nodes, tw, with_mlp, dt, h_out);
+    wa.u = u;
+    wa.pos_x = pos_x;
+    wa.pos_t = pos_t;
+    wa.vars = vars;
+    wa.dt_cum = dt_cum;
+    wa.tw = tw;
+    wa.nv = nv;
     hipStream_t st = (hipStream_t)stream;
     timing_begin(MSMP_K_LEM, st);
-    if (g_lem_split == 5) {
-        const unsigned g1 = (unsigned)((n_nodes + 63) / 64);
-        if (!two_d) switch (ninp) {
-            case 3: hipLaunchKernelGGL((lem_encoder_ws1_kernel<3, 1>), dim3(g1), dim3(256), 0, st, wa); break;
-            case 4: hipLaunchKernelGGL((lem_encoder_ws1_kernel<4, 1>), dim3(g1), dim3(256), 0, st, wa); break;
-            case 5: hipLaunchKernelGGL((lem_encoder_ws1_kernel<5, 1>), dim3(g1), dim3(256), 0, st, wa); break;
-            case 6: hipLaunchKernelGGL((lem_encoder_ws1_kernel<6, 1>), dim3(g1), dim3(256), 0, st, wa); break;
-            case 7: hipLaunchKernelGGL((lem_encoder_ws1_kernel<7, 1>), dim3(g1), dim3(256), 0, st, wa); break;
-            default: hipLaunchKernelGGL((lem_encoder_ws1_kernel<8, 1>), dim3(g1), dim3(256), 0, st, wa); break;
-        } else switch (ninp) {
-            case 4: hipLaunchKernelGGL((lem_encoder_ws1_kernel<4, 2>), dim3(g1), dim3(256), 0, st, wa); break;
-            case 5: hipLaunchKernelGGL((lem_encoder_ws1_kernel<5, 2>), dim3(g1), dim3(256), 0, st, wa); break;
-            case 6: hipLaunchKernelGGL((lem_encoder_ws1_kernel<6, 2>), dim3(g1), dim3(256), 0, st, wa); break;
-            case 7: hipLaunchKernelGGL((lem_encoder_ws1_kernel<7, 2>), dim3(g1), dim3(256), 0, st, wa); break;
-            default: hipLaunchKernelGGL((lem_encoder_ws1_kernel<8, 2>), dim3(g1), dim3(256), 0, st, wa); break;
-        }
-    } else
-    if (g_lem_split == 4) {
-        if (!two_d) switch (ninp) {
-            case 3: hipLaunchKernelGGL((lem_encoder_ws3_kernel<3, 1>), dim3(g96), dim3(512), 0, st, wa); break;
-            case 4: hipLaunchKernelGGL((lem_encoder_ws3_kernel<4, 1>), dim3(g96), dim3(512), 0, st, wa); break;
-            case 5: hipLaunchKernelGGL((lem_encoder_ws3_kernel<5, 1>), dim3(g96), dim3(512), 0, st, wa); break;
-            case 6: hipLaunchKernelGGL((lem_encoder_ws3_kernel<6, 1>), dim3(g96), dim3(512), 0, st, wa); break;
-            case 7: hipLaunchKernelGGL((lem_encoder_ws3_kernel<7, 1>), dim3(g96), dim3(512), 0, st, wa); break;
-            default: hipLaunchKernelGGL((lem_encoder_ws3_kernel<8, 1>), dim3(g96), dim3(512), 0, st, wa); break;
-        } else switch (ninp) {
-            case 4: hipLaunchKernelGGL((lem_encoder_ws3_kernel<4, 2>), dim3(g96), dim3(512), 0, st, wa); break;
-            case 5: hipLaunchKernelGGL((lem_encoder_ws3_kernel<5, 2>), dim3(g96), dim3(512), 0, st, wa); break;
-            case 6: hipLaunchKernelGGL((lem_encoder_ws3_kernel<6, 2>), dim3(g96), dim3(512), 0, st, wa); break;
-            case 7: hipLaunchKernelGGL((lem_encoder_ws3_kernel<7, 2>), dim3(g96), dim3(512), 0, st, wa); break;
-            default: hipLaunchKernelGGL((lem_encoder_ws3_kernel<8, 2>), dim3(g96), dim3(512), 0, st, wa); break;
-        }
-    } else
-    if (!two_d) switch (ninp) {
-        case 3: hipLaunchKernelGGL((lem_encoder_ws_kernel<3, 1>), dim3(g64), dim3(512), 0, st, wa); break;
-        case 4: hipLaunchKernelGGL((lem_encoder_ws_kernel<4, 1>), dim3(g64), dim3(512), 0, st, wa); break;
-        case 5: hipLaunchKernelGGL((lem_encoder_ws_kernel<5, 1>), dim3(g64), dim3(512), 0, st, wa); break;
-        case 6: hipLaunchKernelGGL((lem_encoder_ws_kernel<6, 1>), dim3(g64), dim3(512), 0, st, wa); break;
-        case 7: hipLaunchKernelGGL((lem_encoder_ws_kernel<7, 1>), dim3(g64), dim3(512), 0, st, wa); break;
-        default: hipLaunchKernelGGL((lem_encoder_ws_kernel<8, 1>), dim3(g64), dim3(512), 0, st, wa); break;
-    } else switch (ninp) {
-        case 4: hipLaunchKernelGGL((lem_encoder_ws_kernel<4, 2>), dim3(g64), dim3(512), 0, st, wa); break;
-        case 5: hipLaunchKernelGGL((lem_encoder_ws_kernel<5, 2>), dim3(g64), dim3(512), 0, st, wa); break;
-        case 6: hipLaunchKernelGGL((lem_encoder_ws_kernel<6, 2>), dim3(g64), dim3(512), 0, st, wa); break;
-        case 7: hipLaunchKernelGGL((lem_encoder_ws_kernel<7, 2>), dim3(g64), dim3(512), 0, st, wa); break;
-        default: hipLaunchKernelGGL((lem_encoder_ws_kernel<8, 2>), dim3(g64), dim3(512), 0, st, wa); break;
-    }
+    if (two_d) lem_ws3_launch<2>(wa, ninp, st);
+    else lem_ws3_launch<1>(wa, ninp, st);
     timing_end(MSMP_K_LEM, st);
-    return check_launch("lem_encoder_ws_kernel");
+    return check_launch("lem_encoder_ws3_kernel");
 }

@@ -1357,8 +1357,6 @@ __global__ __launch_bounds__(256, 2) void node_tail_split_kernel(TailArgs a) {
 
 using namespace msmp;
 
-extern int g_lem_split;
-extern int g_lem_nodes;
 extern int g_lem_tail;
 extern int g_lem_share;
 // the sticky range status is the fp16-split path's: the exact-fp32 kernels have no range to leave (they run the data the split path could not)
@@ -1442,9 +1440,7 @@ extern "C" int msmp_tune(const char* key, int value) {
     if (key && !strcmp(key, "lem_tail")) { g_lem_tail = value != 0; return MSMP_OK; }
     if (key && !strcmp(key, "lem_share") && value >= 1 && value <= 16) { g_lem_share = value; return MSMP_OK; }
     if (key && !strcmp(key, "edge_nb")) { g_edge_nb = value; return MSMP_OK; }
-    if (key && !strcmp(key, "lem")) { g_lem_split = value; return MSMP_OK; }
-    if (key && !strcmp(key, "lem_nodes")) { g_lem_nodes = value; return MSMP_OK; }
-    if (key && !strcmp(key, "split")) { g_split = value; g_lem_split = value ? 4 : 0; return MSMP_OK; }
+    if (key && !strcmp(key, "split")) { g_split = value; return MSMP_OK; }
     msmp::set_error("msmp_tune: unknown key");
     return MSMP_ERR_ARG;
 }

@@ -178,7 +178,7 @@ class LEM(nn.Module):
 
     def encode_nodes(self, u, pos_x, pos_t, variables, dt_cum, two_d, mlp=None):
         """Same as `encode` with the step inputs assembled inside the kernel from the node arrays (models_gnn.py:1357-1360 /
-        models_gnn2D.py:429-433).  Returns None when the selected kernel edition has no such entry (msmp_tune "lem" != 3)."""
+        models_gnn2D.py:429-433).  Returns None on the exact-fp32 path (msmp_tune "split" 0), which has no such entry."""
         L = lib()
         n, nv = u.shape[0], variables.shape[1]
         tw = u.shape[1] // (2 if two_d else 1)

@@ -1,5 +1,5 @@
-"""A/B of msmp_tune settings on the default bench workload in ONE gpurun call (separate processes, interleaved):
-    python scripts/ab_tune.py [rounds] [bench args ...] -- tile_persist=0 tile_persist=3 "lem=3,tile_persist=2" """
+"""A/B of msmp_tune settings on the default bench workload on ONE box (separate processes, interleaved):
+    python scripts/ab_tune.py [rounds] [bench args ...] -- tile=2 tile=1 "lem_tail=0,pair=2" """
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 argv = sys.argv[1:]

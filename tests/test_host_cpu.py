@@ -40,7 +40,7 @@ def test_cabi_exports_every_declared_symbol(mp):
     assert L.msmp_packed_layer_floats(25, 99) == -1
 
 
-def test_argument_errors_are_reported_not_thrown(mp):
+def test_argument_errors_and_retired_tune_keys_are_reported_not_thrown(mp):
     L = mp.lib()
     rc = L.msmp_scatter_mean_f32(None, None, 10, None, None)
     assert rc == -1 and b'null pointer' in L.msmp_last_error()
@@ -60,10 +60,11 @@ def test_argument_errors_are_reported_not_thrown(mp):
     assert L.msmp_mlp2_input_stride(28) == 32 and L.msmp_mlp2_input_stride(59) == 64
     assert L.msmp_mp_layer_bwd_f32(*([None] * 11), 10, 20, 1, 25, 2, None, None, 1, 1e-5, None, None, None, None, 0, None) == -1
     assert L.msmp_mp_layer_bwd_workspace_bytes(0, 5, 25, 2, 1) == 0 and L.msmp_mp_layer_bwd_workspace_bytes(100, 588, 25, 2, 1) > 0
-    # knobs: known keys are accepted, unknown ones rejected with a message
-    for key in (b'split', b'edge_nb', b'tail', b'pair', b'lem', b'lem_nodes', b'tile'):
-        assert L.msmp_tune(key, {b'split': 1, b'tail': 1, b'lem': 3, b'lem_nodes': 1, b'pair': 1, b'tile': 2}.get(key, 0)) == 0, key
-    assert L.msmp_tune(b'no_such_knob', 1) != 0 and b'unknown key' in L.msmp_last_error()
+    # knobs: known keys are accepted, unknown ones rejected with a message ("lem" / "lem_nodes" are retired: "split" selects the LEM kernel)
+    for key in (b'split', b'edge_nb', b'tail', b'pair', b'tile'):
+        assert L.msmp_tune(key, {b'split': 1, b'tail': 1, b'pair': 1, b'tile': 2}.get(key, 0)) == 0, key
+    for key in (b'no_such_knob', b'lem', b'lem_nodes'):
+        assert L.msmp_tune(key, 1) != 0 and b'unknown key' in L.msmp_last_error(), key
 
 
 @pytest.mark.parametrize('exp', ['E2', 'WE3', 'RPU', 'MSWG3'])
