@@ -223,7 +223,9 @@ int msmp_build_tiles(const int32_t* rowptr, const int32_t* col, int64_t n_nodes,
  * LDS) or, with p == q == NULL, as msmp_node_project_f32 + msmp_edge_aggregate_projected_f32 in ONE launch: the tile's h / u /
  * pos / vars rows are staged in LDS, P and Q of the tile's nodes are computed there (halo nodes recomputed per tile) and never
  * touch HBM.  feat (may be NULL): the packed [u | pos | vars] rows of msmp_pack_node_features_f32; they are the same for every
- * layer of a forward, so packing them once saves each layer's tile staging the scalar loads of those columns. */
+ * layer of a forward, so packing them once saves each layer's tile staging the scalar loads of those columns.
+ * Folded form (p == q == NULL): tw + 1 + nv <= 128 (up to four 32-column tail chunks); the staged form takes any width.
+ * msmp_node_feature_stride: 32 x the tail chunks (-1 for invalid sizes); msmp_prepare_nodes accepts strides up to 128. */
 int msmp_node_feature_stride(int tw, int nv);
 /* Feature preparation of Solver.forward (experiments/models_gnn.py:1325-1352; models_gnn2D.py:104-116) in one launch: x [N,tw] and
  * pos [N,2] = (t, x) in float32 or float64 (*_f64 flags), n_cols per-node parameter columns [N] (`cols`, `col_f64`, host arrays)
@@ -414,7 +416,8 @@ int msmp_lem_train_bwd_f32(const float* grad_y, const float* saved, const float*
  * single layer.  u, pos, vars carry no gradient.  GEMMs with edge- / node-sized outputs run on rocBLAS (looked up in the
  * process at run time: MSMP_ERR_UNSUPPORTED if librocblas cannot be loaded).  src_rowptr [N+1] / src_perm [E] (both or
  * neither): the CSR edge ids regrouped by SOURCE node, ascending inside a source; with them dh's source-side scatter runs in
- * that fixed order (bitwise reproducible gradients), without them it uses float atomics.  tw + 1 + nv <= 64.
+ * that fixed order (bitwise reproducible gradients), without them it uses float atomics.  tw + 1 + nv <= 128; above 64 (2-D windows
+ * of 50) only with src_rowptr / src_perm and the own GEMMs (tune "bwd_gemm" != 0), else MSMP_ERR_UNSUPPORTED.
  * Workspace: msmp_mp_layer_bwd_workspace_bytes (0 for invalid sizes). */
 size_t msmp_mp_layer_bwd_workspace_bytes(int64_t n_nodes, int64_t n_edges, int tw, int nv, int gated);
 int msmp_mp_layer_bwd_f32(const float* grad_out, const float* h, const float* u, const float* pos, const float* vars,
@@ -451,7 +454,8 @@ int msmp_sqerr_sum_f32(const float* a, const float* b, int64_t n, float* out, vo
                        msmp_stream_t stream);
 
 /* The per-edge input of message_net_1 (models_gnn.py:69-75): out[e] = cat(h[i], h[j], u[i]-u[j], pos[i]-pos[j], vars[i]),
- * i = tgt[e], j = col[e]; out [E, ld] with ld >= 256 + tw + 1 + nv a multiple of 4 (columns past the concat are not written). */
+ * i = tgt[e], j = col[e]; out [E, ld] with ld >= 256 + tw + 1 + nv a multiple of 4 (columns past the concat are not written);
+ * tw + 1 + nv <= 128. */
 int msmp_edge_concat_f32(const float* h, const float* u, const float* pos, const float* vars, const int32_t* tgt,
                          const int32_t* col, int64_t n_edges, int tw, int nv, int ld, float* out, msmp_stream_t stream);
 /* Backward of aggr='mean' (:42,107) fused with the derivative of message_net_2's Swish:

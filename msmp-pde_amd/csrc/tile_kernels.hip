@@ -193,7 +193,7 @@ __device__ __forceinline__ float prep_div(const void* p, int f64, long i, double
 }
 __global__ __launch_bounds__(256) void prepare_nodes_kernel(PrepArgs a) {
     // thread = (node, four consecutive columns of the packed row): one 16-byte store of the feature row per thread
-    const int groups = a.stride >> 2;                                  // 8, 16 or 24
+    const int groups = a.stride >> 2;                                  // 8, 16, 24 or 32
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= a.n * groups) return;
     const long node = groups == 8 ? i >> 3 : (groups == 16 ? i >> 4 : i / groups);
@@ -295,8 +295,14 @@ __device__ __forceinline__ void whalf_dma(const float* __restrict__ half_chunk, 
 
 using half4v = __attribute__((ext_vector_type(4))) _Float16;
 
-template <int MODE, bool LISTED>
+// NT: tail chunks the folded projections are built for (2: tw + 1 + nv <= 64, the 1-D classes and 2-D windows of 25;  4: <= 128,
+// 2-D windows of 50).  With 2 the fragment tile holds 4 h rows, then P- and Q-tail rows per tail chunk.  Four chunks of both would be 12
+// rows (74 KB: past the three-workgroup LDS cut), so with 4 the tile holds 4 h rows and the 4 P-tail rows only: Q's tail is -(u, pos)
+// with zero variables, i.e. the P-tail fragment times a per-column sign mask, applied to the fragment in registers where it is read
+// (v_pk_mul_f16 by -1 / 0: exact, the same values the staged Q rows of NT = 2 hold).
+template <int MODE, bool LISTED, int NT = 2>
 __device__ __forceinline__ void edge_tile_body(const TileArgs& a, float* lds) {
+    static_assert(NT == 2 || NT == 4, "tail chunks of the folded projections: 2 or 4");
     constexpr bool FOLD = MODE != 0;
     float* wbuf = lds;                               // W2 half chunks (2 x 8 KB)
     float* pl = lds + WBUF_FLOATS;             // P rows [32][PQLD]
@@ -408,8 +414,11 @@ __device__ __forceinline__ void edge_tile_body(const TileArgs& a, float* lds) {
         };
         half8 wp[3][2][2], wq[3][2][2];
         f32x4 b1v[4];
+        // i < 4: chunk i of h_i (P) and of h_j (Q);  i = 4: tail chunks 8, 9 (NT = 4 and i = 5: 10, 11), one per array (a chunk past
+        // the tail repeats chunk 8: a valid address, never multiplied)
         auto wload = [&](int i) {
-            const int chp = i < 4 ? i : 8, chq = i < 4 ? 4 + i : (ntail > 1 ? 9 : 8);
+            const int chp = i < 4 ? i : (NT == 4 && i == 5 ? (ntail > 2 ? 10 : 8) : 8);
+            const int chq = i < 4 ? 4 + i : (NT == 4 && i == 5 ? (ntail > 3 ? 11 : 8) : (ntail > 1 ? 9 : 8));
 #pragma unroll
             for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -420,13 +429,13 @@ __device__ __forceinline__ void edge_tile_body(const TileArgs& a, float* lds) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) hv[i] = *reinterpret_cast<const f32x4*>(a.h + (size_t)rnode[i] * H + 4 * (tid & 31));
             const int g = tid & 7;
-            float tx[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+            float tx[NT][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};       // (NT = 4: the rest zero-initialised as well)
             if (packed_feat) {
                 // loaded on BOTH sides of `jc < ntail` (a second copy of piece 0 where there is no second chunk) and selected afterwards: as a
                 // load inside the branch, the value was merged with the zeros of the other side by a copy right behind it, and that copy
                 // waited (vmcnt(0)) for every row load issued above before the weight prefetches below could be requested
 #pragma unroll
-                for (int jc = 0; jc < 2; ++jc) {
+                for (int jc = 0; jc < NT; ++jc) {
                     const bool on = jc < ntail;
                     const f32x4 fv = *reinterpret_cast<const f32x4*>(a.feat + (size_t)fnode * (32 * ntail) + 32 * (on ? jc : 0) + 4 * g);
 #pragma unroll
@@ -434,7 +443,7 @@ __device__ __forceinline__ void edge_tile_body(const TileArgs& a, float* lds) {
                 }
             } else {
 #pragma unroll
-                for (int jc = 0; jc < 2; ++jc)
+                for (int jc = 0; jc < NT; ++jc)
                     if (jc < ntail) {
 #pragma unroll
                         for (int m = 0; m < 4; ++m) {
@@ -463,6 +472,19 @@ __device__ __forceinline__ void edge_tile_body(const TileArgs& a, float* lds) {
                 *reinterpret_cast<half4v*>(row) = half4v{h01[0], h01[1], h23[0], h23[1]};
                 *reinterpret_cast<half4v*>(row + 32) = half4v{l01[0], l01[1], l23[0], l23[1]};
             }
+            if constexpr (NT == 4) {
+#pragma unroll
+                for (int jc = 0; jc < NT; ++jc) {
+                    if (jc < ntail) {      // the P-tail rows only (Q's are derived from them where they are read)
+                        half2v ph[2], pl2[2];
+#pragma unroll
+                        for (int m = 0; m < 2; ++m) split_node_pair(tx[jc][2 * m], tx[jc][2 * m + 1], ph[m], pl2[m]);
+                        _Float16* rp_ = bt + frag_row(4 + jc, tid >> 3) + 4 * g;
+                        *reinterpret_cast<half4v*>(rp_) = half4v{ph[0][0], ph[0][1], ph[1][0], ph[1][1]};
+                        *reinterpret_cast<half4v*>(rp_ + 32) = half4v{pl2[0][0], pl2[0][1], pl2[1][0], pl2[1][1]};
+                    }
+                }
+            } else {
 #pragma unroll
             for (int jc = 0; jc < 2; ++jc) {
                 if (jc < ntail) {
@@ -483,6 +505,7 @@ __device__ __forceinline__ void edge_tile_body(const TileArgs& a, float* lds) {
                     *reinterpret_cast<half4v*>(rq_) = half4v{qh[0][0], qh[0][1], qh[1][0], qh[1][1]};
                     *reinterpret_cast<half4v*>(rq_ + 32) = half4v{ql2[0][0], ql2[0][1], ql2[1][0], ql2[1][1]};
                 }
+            }
             }
         }
         __syncthreads();
@@ -517,7 +540,7 @@ __device__ __forceinline__ void edge_tile_body(const TileArgs& a, float* lds) {
 #pragma unroll
         for (int ch = 0; ch < 4; ++ch) {
             const int cur = ch % 3;
-            if (ch + 2 < 4 || (ch + 2 == 4 && ntail > 0)) wload(ch + 2);
+            if (ch + 2 < 4 || (ch + 2 == 4 && ntail > 0) || (NT == 4 && ch + 2 == 5 && ntail > 2)) wload(ch + 2);
             half8 ahi[2], alo[2];
             afrag(ch, ahi, alo);
 #pragma unroll
@@ -526,6 +549,29 @@ __device__ __forceinline__ void edge_tile_body(const TileArgs& a, float* lds) {
                 mma3(accQ, ahi[s], alo[s], wq[cur][s][0], wq[cur][s][1]);
             }
         }
+        if constexpr (NT == 4) {
+            // tail chunk jc: weights in wp[1], wq[1], wp[2], wq[2];  Q's fragment = P's times the sign mask of its columns
+            // 32 jc + 16 s + 8 hh + e:  -1 for u and pos (column <= tw), 0 for the variables and the padding
+#pragma unroll
+            for (int jc = 0; jc < NT; ++jc) {
+                if (jc < ntail) {
+                    half8 phi[2], plo[2];
+                    afrag(4 + jc, phi, plo);
+#pragma unroll
+                    for (int s = 0; s < 2; ++s) {
+                        const int n = a.tw - (32 * jc + 16 * s + 8 * hh);
+                        half8 nm;
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) nm[e] = (_Float16)(e <= n ? -1.f : 0.f);
+                        const half8 qhi = phi[s] * nm, qlo = plo[s] * nm;
+                        const half8 whi = (jc & 1) ? wq[1 + (jc >> 1)][s][0] : wp[1 + (jc >> 1)][s][0];
+                        const half8 wlo = (jc & 1) ? wq[1 + (jc >> 1)][s][1] : wp[1 + (jc >> 1)][s][1];
+                        mma3(accP, phi[s], plo[s], whi, wlo);
+                        mma3(accQ, qhi, qlo, whi, wlo);
+                    }
+                }
+            }
+        } else
         for (int jc = 0; jc < ntail; ++jc) {
             half8 phi[2], plo[2], qhi[2], qlo[2];
             afrag(4 + 2 * jc, phi, plo);
@@ -785,6 +831,12 @@ __global__ __launch_bounds__(256, 3) void edge_tile_kernel(TileArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[TILE_LDS_FLOATS];
     edge_tile_body<MODE, LISTED>(a, lds);
 }
+// the folded modes for three or four tail chunks (tw + 1 + nv in 65..128: 2-D windows of 50); same LDS, same occupancy
+template <int MODE, bool LISTED>
+__global__ __launch_bounds__(256, 3) void edge_tile4_kernel(TileArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[TILE_LDS_FLOATS];
+    edge_tile_body<MODE, LISTED, 4>(a, lds);
+}
 
 // Both heads of a gated pair in ONE launch (blockIdx.y = head; same body, bit-identical results): small batches are bound by the
 // latency of their dependent launches, and with the projections folded in a gated pair is then two launches (this + the node tail).
@@ -795,6 +847,11 @@ template <int MODE, bool LISTED>
 __global__ __launch_bounds__(256, 3) void edge_tile_pair_kernel(TileArgs2 a) {
     __shared__ __attribute__((aligned(16))) float lds[TILE_LDS_FLOATS];
     edge_tile_body<MODE, LISTED>(a.head[blockIdx.y], lds);
+}
+template <int MODE, bool LISTED>
+__global__ __launch_bounds__(256, 3) void edge_tile4_pair_kernel(TileArgs2 a) {
+    __shared__ __attribute__((aligned(16))) float lds[TILE_LDS_FLOATS];
+    edge_tile_body<MODE, LISTED, 4>(a.head[blockIdx.y], lds);
 }
 
 }  // namespace msmp
@@ -831,7 +888,7 @@ extern "C" int msmp_prepare_nodes(const void* x, int x_f64, const void* pos, int
                  "msmp_prepare_nodes: null pointer");
     MSMP_REQUIRE(n_nodes > 0 && tw > 0 && n_cols >= 0 && n_cols < MSMP_MAX_VARS, MSMP_ERR_ARG, "msmp_prepare_nodes: bad sizes");
     const int stride = msmp_node_feature_stride(tw, 1 + n_cols);
-    MSMP_REQUIRE(stride > 0 && stride <= 64 + 32, MSMP_ERR_ARG, "msmp_prepare_nodes: bad sizes");
+    MSMP_REQUIRE(stride > 0 && stride <= 128, MSMP_ERR_ARG, "msmp_prepare_nodes: bad sizes");
     PrepArgs a{};
     a.x = x; a.pos = pos; a.x_f64 = x_f64; a.pos_f64 = pos_f64; a.n_cols = n_cols; a.L = L; a.tmax = tmax; a.n = (long)n_nodes; a.tw = tw;
     a.stride = stride; a.u = u_out; a.pos_x = pos_x_out; a.pos_t = pos_t_out; a.vars = vars_out; a.feat = feat_out;
@@ -893,6 +950,13 @@ static TileArgs tile_args(const float* h, const float* u, const float* pos, cons
 
 template <int MODE>
 static void launch_tiles(const TileArgs& a, bool listed, unsigned n_tiles, hipStream_t st) {
+    if constexpr (MODE != 0) {
+        if (a.nc1 - 8 > 2) {          // the folded projections of 3..4 tail chunks
+            if (listed) hipLaunchKernelGGL((edge_tile4_kernel<MODE, true>), dim3(n_tiles), dim3(256), 0, st, a);
+            else hipLaunchKernelGGL((edge_tile4_kernel<MODE, false>), dim3(n_tiles), dim3(256), 0, st, a);
+            return;
+        }
+    }
     if (listed) hipLaunchKernelGGL((edge_tile_kernel<MODE, true>), dim3(n_tiles), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((edge_tile_kernel<MODE, false>), dim3(n_tiles), dim3(256), 0, st, a);
 }
@@ -910,7 +974,7 @@ extern "C" int msmp_edge_aggregate_tiled_f32(const float* h, const float* u, con
                  MSMP_ERR_ARG, "msmp_edge_aggregate_tiled_f32: bad sizes");
     MSMP_REQUIRE(msmp_tune_get("split"), MSMP_ERR_UNSUPPORTED, "msmp_edge_aggregate_tiled_f32: only on the fp16-split matrix path");
     const PackedLayout L = packed_layout(tw, nv);
-    MSMP_REQUIRE(!fold || L.nc1 - 8 <= 2, MSMP_ERR_UNSUPPORTED, "msmp_edge_aggregate_tiled_f32: tw + 1 + nv <= 64");
+    MSMP_REQUIRE(!fold || L.nc1 - 8 <= 4, MSMP_ERR_UNSUPPORTED, "msmp_edge_aggregate_tiled_f32: tw + 1 + nv <= 128");
     const TileArgs a = tile_args(h, u, pos, vars, feat, p, q, rowptr, tiles, n_nodes, n_edges, tw, nv, L, packed, agg_out);
     hipStream_t st = (hipStream_t)stream;
     timing_begin(MSMP_K_EDGE_MLP, st);
@@ -930,7 +994,7 @@ int msmp_edge_aggregate_tiled_pair(const float* h, const float* u, const float* 
                  "msmp_edge_aggregate_tiled_pair: null pointer");
     MSMP_REQUIRE(msmp_tiles_ok(tiles, n_nodes), MSMP_ERR_ARG, "msmp_edge_aggregate_tiled_pair: the tile descriptor does not cover %ld nodes", (long)n_nodes);
     const PackedLayout L = packed_layout(tw, nv);
-    MSMP_REQUIRE(L.nc1 - 8 <= 2 && msmp_tune_get("split"), MSMP_ERR_UNSUPPORTED, "msmp_edge_aggregate_tiled_pair: unsupported configuration");
+    MSMP_REQUIRE(L.nc1 - 8 <= 4 && msmp_tune_get("split"), MSMP_ERR_UNSUPPORTED, "msmp_edge_aggregate_tiled_pair: unsupported configuration");
     TileArgs2 a2;
     a2.head[0] = tile_args(h, u, pos, vars, feat, nullptr, nullptr, rowptr, tiles, n_nodes, n_edges, tw, nv, L, packed_a, agg_a);
     a2.head[1] = tile_args(h, u, pos, vars, feat, nullptr, nullptr, rowptr, tiles, n_nodes, n_edges, tw, nv, L, packed_b, agg_b);
@@ -938,7 +1002,12 @@ int msmp_edge_aggregate_tiled_pair(const float* h, const float* u, const float* 
     timing_begin(MSMP_K_EDGE_MLP, st);
     const dim3 grid((unsigned)tiles->n_tiles, 2);
     const bool listed = tiles->listed != 0 || !msmp_tune_get("tile_arith");
-    if (feat && listed) hipLaunchKernelGGL((edge_tile_pair_kernel<2, true>), grid, dim3(256), 0, st, a2);
+    if (L.nc1 - 8 > 2) {          // 3..4 tail chunks
+        if (feat && listed) hipLaunchKernelGGL((edge_tile4_pair_kernel<2, true>), grid, dim3(256), 0, st, a2);
+        else if (feat) hipLaunchKernelGGL((edge_tile4_pair_kernel<2, false>), grid, dim3(256), 0, st, a2);
+        else if (listed) hipLaunchKernelGGL((edge_tile4_pair_kernel<1, true>), grid, dim3(256), 0, st, a2);
+        else hipLaunchKernelGGL((edge_tile4_pair_kernel<1, false>), grid, dim3(256), 0, st, a2);
+    } else if (feat && listed) hipLaunchKernelGGL((edge_tile_pair_kernel<2, true>), grid, dim3(256), 0, st, a2);
     else if (feat) hipLaunchKernelGGL((edge_tile_pair_kernel<2, false>), grid, dim3(256), 0, st, a2);
     else if (listed) hipLaunchKernelGGL((edge_tile_pair_kernel<1, true>), grid, dim3(256), 0, st, a2);
     else hipLaunchKernelGGL((edge_tile_pair_kernel<1, false>), grid, dim3(256), 0, st, a2);

@@ -24,9 +24,11 @@ __global__ __launch_bounds__(256) void edge_concat_kernel(const float* __restric
         float* row = out + (size_t)e * ld;
         const int node = lane < 32 ? i : j;
         *reinterpret_cast<f32x4*>(row + 4 * lane) = *reinterpret_cast<const f32x4*>(h + (size_t)node * H + 4 * (lane & 31));
-        if (lane < tw) row[2 * H + lane] = u[(size_t)i * tw + lane] - u[(size_t)j * tw + lane];
-        else if (lane == tw) row[2 * H + tw] = pos[i] - pos[j];
-        else if (lane < tw + 1 + nv) row[2 * H + lane] = vars[(size_t)i * nv + (lane - tw - 1)];
+        for (int k = lane; k < tw + 1 + nv; k += 64) {          // tail column k (one pass up to 64 columns, two up to 128)
+            if (k < tw) row[2 * H + k] = u[(size_t)i * tw + k] - u[(size_t)j * tw + k];
+            else if (k == tw) row[2 * H + tw] = pos[i] - pos[j];
+            else row[2 * H + k] = vars[(size_t)i * nv + (k - tw - 1)];
+        }
     }
 }
 
@@ -142,7 +144,7 @@ extern "C" int msmp_edge_concat_f32(const float* h, const float* u, const float*
                                     const int32_t* col, int64_t n_edges, int tw, int nv, int ld, float* out, msmp_stream_t stream) {
     MSMP_REQUIRE(h && u && pos && vars && tgt && col && out, MSMP_ERR_ARG, "msmp_edge_concat_f32: null pointer");
     MSMP_REQUIRE(n_edges >= 0 && n_edges < (1L << 31) && tw >= 1 && nv >= 1 && nv <= MSMP_MAX_VARS, MSMP_ERR_ARG, "msmp_edge_concat_f32: bad sizes");
-    MSMP_REQUIRE(tw + 1 + nv <= 64, MSMP_ERR_UNSUPPORTED, "msmp_edge_concat_f32: tw + 1 + nv = %d > 64", tw + 1 + nv);
+    MSMP_REQUIRE(tw + 1 + nv <= 128, MSMP_ERR_UNSUPPORTED, "msmp_edge_concat_f32: tw + 1 + nv = %d > 128", tw + 1 + nv);
     MSMP_REQUIRE(ld >= 2 * H + tw + 1 + nv && ld % 4 == 0, MSMP_ERR_ARG, "msmp_edge_concat_f32: row stride %d (need a multiple of 4 >= %d)", ld,
                  2 * H + tw + 1 + nv);
     if (n_edges == 0) return MSMP_OK;
@@ -716,19 +718,19 @@ struct HeadBuf {      // per head: recompute intermediates and gradient scratch
     float *feat, *P, *Q, *st, *ss, *wp, *wq, *t1, *t2, *tb;
 };
 static int fact_ldf(int tw, int nv) { return H + 32 * ((tw + 1 + nv + 31) / 32); }
+// row stride the workspace reserves for F, WP, WQ, t1, t2: H + 64 (every tw + 1 + nv <= 64, the sizes of before), H + 128 above
+static int ws_ldf(int tw, int nv) { return tw + 1 + nv <= 64 ? H + 64 : fact_ldf(tw, nv); }
 
-static size_t head_floats(long n, long e, int ld_e, int ld_n) {
-    const int ldf = H + 64;      // upper bound of fact_ldf (tw + 1 + nv <= 64)
+static size_t head_floats(long n, long e, int ld_e, int ld_n, int ldf) {
     return (size_t)e * (ld_e + 5 * H + 2 * H) + (size_t)n * (H + ld_n + 5 * H + 2 * H) + (size_t)n * (ldf + 4 * H) + 4 * (size_t)H * ldf + H + 10 * 64;
 }
 
-static void carve(float*& p, long n, long e, int ld_e, int ld_n, HeadBuf& b) {
+static void carve(float*& p, long n, long e, int ld_e, int ld_n, int ldf, HeadBuf& b) {
     auto take = [&](size_t k) { float* r = p; p += (k + 63) / 64 * 64; return r; };
     b.cat_e = take((size_t)e * ld_e); b.a1 = take((size_t)e * H); b.m1 = take((size_t)e * H); b.a2 = take((size_t)e * H);
     b.x2 = take((size_t)e * H); b.x1 = take((size_t)e * H); b.dcat_e = take((size_t)e * 2 * H);
     b.agg = take((size_t)n * H); b.cat_n = take((size_t)n * ld_n); b.a3 = take((size_t)n * H); b.u1 = take((size_t)n * H);
     b.upd = take((size_t)n * H); b.dupd = take((size_t)n * H); b.x3 = take((size_t)n * H); b.dcat_n = take((size_t)n * 2 * H);
-    const int ldf = H + 64;
     b.feat = take((size_t)n * ldf); b.P = take((size_t)n * H); b.Q = take((size_t)n * H); b.st = take((size_t)n * H); b.ss = take((size_t)n * H);
     b.wp = take((size_t)H * ldf); b.wq = take((size_t)H * ldf); b.t1 = take((size_t)H * ldf); b.t2 = take((size_t)H * ldf); b.tb = take(H);
 }
@@ -1013,14 +1015,14 @@ struct HeadFrags {
     u32x4 *w4t, *w3t[2], *w2t, *w1t[2];  // data-gradient forms (reduction over the 128 output channels; 128-column groups of the input)
     u32x4 *wp, *wq;                      // factorised message_net_1: the per-node projections (K = fact_ldf)
 };
-static size_t head_frag_u4(int kmsg, int kupd) {
-    return (size_t)RG_CHUNK_U4 * ((kmsg + 31) / 32 + 4 + (kupd + 31) / 32 + 4 + 6 * 4 + 2 * 6);
+static size_t head_frag_u4(int kmsg, int kupd, int ldf) {
+    return (size_t)RG_CHUNK_U4 * ((kmsg + 31) / 32 + 4 + (kupd + 31) / 32 + 4 + 6 * 4 + 2 * (ldf / 32));
 }
-static void carve_frags(u32x4*& p, int kmsg, int kupd, HeadFrags& f) {
+static void carve_frags(u32x4*& p, int kmsg, int kupd, int ldf, HeadFrags& f) {
     auto take = [&](int chunks) { u32x4* r = p; p += (size_t)chunks * RG_CHUNK_U4; return r; };
     f.w1 = take((kmsg + 31) / 32); f.w2 = take(4); f.w3 = take((kupd + 31) / 32); f.w4 = take(4);
     f.w4t = take(4); f.w3t[0] = take(4); f.w3t[1] = take(4); f.w2t = take(4); f.w1t[0] = take(4); f.w1t[1] = take(4);
-    f.wp = take(6); f.wq = take(6);
+    f.wp = take(ldf / 32); f.wq = take(ldf / 32);
 }
 static void add_pack(RgPackArgs& a, int& blocks, const float* w, int ldw, int K, int col0, int transposed, u32x4* out) {
     RgPackJob& j = a.job[a.n_jobs++];
@@ -1165,7 +1167,8 @@ static int64_t bwd_gw_floats(long n, long e, int kmsg, int kupd, int heads) {
         if (e) { rows[j] = e; k2[j++] = kmsg; rows[j] = e; k2[j++] = H; }
         rows[j] = n; k2[j++] = kupd; rows[j] = n; k2[j++] = H;
     }
-    const int64_t plain = msmp_grad_weights_workspace_floats(j, rows, k2);
+    // (tw + 1 + nv > 64: kmsg > 319 is past the weight-gradient kernel; such layers take the factorised form only)
+    const int64_t plain = kmsg - 2 * H <= 64 ? msmp_grad_weights_workspace_floats(j, rows, k2) : 0;
     j = 0;                                  // factorised message_net_1: two node-sized jobs instead of the [E, kmsg] one
     for (int hd = 0; hd < heads; ++hd) {
         if (e) { rows[j] = n; k2[j++] = kmsg - H; rows[j] = n; k2[j++] = kmsg - H; rows[j] = e; k2[j++] = H; }
@@ -1256,9 +1259,10 @@ extern "C" size_t msmp_mp_layer_bwd_workspace_bytes(int64_t n_nodes, int64_t n_e
     const int kmsg = 2 * H + tw + 1 + nv, kupd = 2 * H + nv, ld_e = (kmsg + 3) / 4 * 4, ld_n = (kupd + 3) / 4 * 4;
     const int heads = gated ? 2 : 1;
     const int64_t gw = bwd_gw_floats(n_nodes, n_edges, kmsg, kupd, heads);
-    if (gw < 0) return 0;
-    return (heads * (head_floats(n_nodes, n_edges, ld_e, ld_n) + 15 * 64) + (size_t)gw + 64) * sizeof(float) + 256 +
-           heads * head_frag_u4(kmsg, kupd) * sizeof(u32x4) + 256;
+    if (gw < 0 || tw + 1 + nv > 128) return 0;
+    const int ldf = ws_ldf(tw, nv);
+    return (heads * (head_floats(n_nodes, n_edges, ld_e, ld_n, ldf) + 15 * 64) + (size_t)gw + 64) * sizeof(float) + 256 +
+           heads * head_frag_u4(kmsg, kupd, ldf) * sizeof(u32x4) + 256;
 }
 
 extern "C" int msmp_mp_layer_bwd_f32(const float* grad_out, const float* h, const float* u, const float* pos, const float* vars,
@@ -1276,7 +1280,7 @@ extern "C" int msmp_mp_layer_bwd_f32(const float* grad_out, const float* h, cons
     MSMP_REQUIRE(mode == MSMP_LAYER_LIN || mode == MSMP_LAYER_RESIDUAL_SWISH, MSMP_ERR_ARG, "msmp_mp_layer_bwd_f32: bad mode %d", mode);
     MSMP_REQUIRE(!gated || mode == MSMP_LAYER_LIN, MSMP_ERR_ARG, "msmp_mp_layer_bwd_f32: the gated pair uses GNN_LayerLin layers");
     MSMP_REQUIRE(n_nodes > 0 && n_edges >= 0 && n_graphs > 0 && n_nodes < (1L << 31) && n_edges < (1L << 31) && tw >= 1 && nv >= 1 &&
-                     nv <= MSMP_MAX_VARS && tw + 1 + nv <= 64, MSMP_ERR_ARG, "msmp_mp_layer_bwd_f32: bad sizes");
+                     nv <= MSMP_MAX_VARS && tw + 1 + nv <= 128, MSMP_ERR_ARG, "msmp_mp_layer_bwd_f32: bad sizes");
     for (int i = 0; i < 8; ++i) {
         MSMP_REQUIRE(params_main[i] && grads_main[i], MSMP_ERR_ARG, "msmp_mp_layer_bwd_f32: null parameter / gradient pointer %d", i);
         MSMP_REQUIRE(!gated || (params_gate[i] && grads_gate[i]), MSMP_ERR_ARG, "msmp_mp_layer_bwd_f32: null gate parameter / gradient pointer %d", i);
@@ -1287,6 +1291,10 @@ extern "C" int msmp_mp_layer_bwd_f32(const float* grad_out, const float* h, cons
     // batch 128 12.8 / 12.1, batch 512 39.0 / 34.0: below that the 128-row workgroups do not fill the chip); tune "bwd_gemm": 0 never, 2 always
     const int bg_mode = msmp_tune_get("bwd_gemm");
     const bool own_gemm = bg_mode != 0;        // 0: rocblas_sgemm (kept for A/B runs); the library is never loaded otherwise
+    // a tail wider than 64 columns (2-D windows of 50) takes the factorised message_net_1 only: the per-edge form's [E, kmsg] weight
+    // gradient (kmsg up to 365) is past the weight-gradient kernel's 319 columns
+    MSMP_REQUIRE(tw + 1 + nv <= 64 || n_edges == 0 || (own_gemm && src_rowptr), MSMP_ERR_UNSUPPORTED,
+                 "msmp_mp_layer_bwd_f32: tw + 1 + nv = %d > 64 needs src_rowptr / src_perm and the own GEMMs (msmp_tune(\"bwd_gemm\") != 0)", tw + 1 + nv);
     static Blas none;
     Blas& bl = own_gemm ? none : blas();
     hipStream_t st = (hipStream_t)stream;
@@ -1301,8 +1309,9 @@ extern "C" int msmp_mp_layer_bwd_f32(const float* grad_out, const float* h, cons
     c.ld_n = (c.kupd + 3) / 4 * 4;
     float* p = reinterpret_cast<float*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
     HeadBuf bm, bg;
-    carve(p, c.n, c.e, c.ld_e, c.ld_n, bm);
-    if (gated) carve(p, c.n, c.e, c.ld_e, c.ld_n, bg);
+    const int ldf_ws = ws_ldf(tw, nv);
+    carve(p, c.n, c.e, c.ld_e, c.ld_n, ldf_ws, bm);
+    if (gated) carve(p, c.n, c.e, c.ld_e, c.ld_n, ldf_ws, bg);
     float* gw_ws = p;
     const int64_t gw_floats = bwd_gw_floats(c.n, c.e, c.kmsg, c.kupd, gated ? 2 : 1);
     const long n4 = c.n * 32;
@@ -1320,11 +1329,11 @@ extern "C" int msmp_mp_layer_bwd_f32(const float* grad_out, const float* h, cons
             hipLaunchKernelGGL(pq_weights_kernel, dim3(grid_for((long)H * ldf)), dim3(256), 0, st, params_main[0], c.kmsg, tw, nv, ldf, bm.wp, bm.wq);
             if (gated) hipLaunchKernelGGL(pq_weights_kernel, dim3(grid_for((long)H * ldf)), dim3(256), 0, st, params_gate[0], c.kmsg, tw, nv, ldf, bg.wp, bg.wq);
         }
-        carve_frags(fp, c.kmsg, c.kupd, fm);
+        carve_frags(fp, c.kmsg, c.kupd, ldf_ws, fm);
         pack_head_frags(params_main, c.kmsg, c.kupd, fm, pa, blocks, fact ? bm.wp : nullptr, bm.wq, ldf);
         frm = &fm;
         if (gated) {
-            carve_frags(fp, c.kmsg, c.kupd, fg);
+            carve_frags(fp, c.kmsg, c.kupd, ldf_ws, fg);
             pack_head_frags(params_gate, c.kmsg, c.kupd, fg, pa, blocks, fact ? bg.wp : nullptr, bg.wq, ldf);
             frg = &fg;
         }
