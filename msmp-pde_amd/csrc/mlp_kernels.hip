@@ -89,11 +89,11 @@ __device__ __forceinline__ void edge_gather(const EdgeArgs& a, int c, int i, int
 // per-workgroup cycle sums of wave 0, kept in scalar registers and added to g_prof once at the end.
 #if MSMP_PROF
 __device__ unsigned long long g_prof[16];
-#define PROF_DECL long long pacc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; long long tp = __builtin_readcyclecounter();
-#define PROF_ARGS , long long& tp, long long (&pacc)[12]
+#define PROF_DECL long long pacc[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; long long tp = __builtin_readcyclecounter();
+#define PROF_ARGS , long long& tp, long long (&pacc)[15]
 #define PROF_PASS , tp, pacc
 #define PROF_MARK(i) do { const long long t_ = __builtin_readcyclecounter(); pacc[i] += t_ - tp; tp = t_; } while (0)
-#define PROF_FLUSH if (tid == 0 && (blockIdx.x & 15) == 0) { for (int i_ = 0; i_ < 12; ++i_) atomicAdd(&g_prof[i_], (unsigned long long)pacc[i_]); atomicAdd(&g_prof[15], 1ull); }   /* one workgroup in 16 reports: see tile_kernels.hip */
+#define PROF_FLUSH if (tid == 0 && (blockIdx.x & 15) == 0) { for (int i_ = 0; i_ < 15; ++i_) atomicAdd(&g_prof[i_], (unsigned long long)pacc[i_]); atomicAdd(&g_prof[15], 1ull); }   /* one workgroup in 16 reports: see tile_kernels.hip */
 #if MSMP_PROF_EDGE
 #define PROF_EDGE(i) PROF_MARK(i)
 #define PROF_EDGE_FLUSH PROF_FLUSH
@@ -976,8 +976,10 @@ struct TailArgs {
 // One update head, update_net_2 transposed: yT[T][r] = 2^s4 (W4 Swish(W3 [h ; agg ; vars] + b3) + b4)[channel 4 c + T]
 // of node acc_row(r, hh) of the wave's 32-node tile (the w4t fragments deal the output channels round-robin over the
 // four tiles, so a lane owns four CONSECUTIVE channels and h / h' move as 16-byte pieces of 512-byte rows).
-// tail_rows_issue starts the LDS-DMA of the first 32-column chunk of the graph's rows (the gated kernel issues the main head's
-// during the gate head's update_net_2); head_compute ends with the weight buffers free.
+// A head is head_chunks (update_net_1, a 32-column chunk of the node rows per iteration) + head_finish (variables, Swish, centring,
+// update_net_2).  The gated kernel stages and splits the h chunks 0..3 ONCE for both heads (its own loop in the kernel), runs the gate
+// head's aggregate chunks and head_finish with the main head's partial sums parked in registers, and requests the main head's first
+// aggregate chunk / next weight chunk inside the gate head's head_finish; head_finish ends with the weight buffers free.
 constexpr float TAIL_ACT_SCALE = 64.0f;       // hidden units of the update net (Swish outputs)
 constexpr float TAIL_NODE_SCALE = 256.0f;     // node rows (h, aggregate, variables): saturating, see tile_kernels.hip
 __device__ __forceinline__ float tail_node_scaled(float x) { return __builtin_amdgcn_fmed3f(x * TAIL_NODE_SCALE, -65504.0f, 65504.0f); }
@@ -1019,24 +1021,11 @@ __device__ __forceinline__ void wstage_dma(const float* __restrict__ chunk, floa
                                          (__attribute__((address_space(3))) void*)(buf + 4 * (tid + 256 * i)), 16, 0, 0);
 }
 
-template <typename MidHook>
-__device__ __forceinline__ void head_compute(float* rowbuf, int n0, int n1, const float* __restrict__ h, const float* __restrict__ agg,
-                                             const float* __restrict__ vars, long nc, int nv, const float* b3, const float* b4,
-                                             const float* w3vh, const float* w3s, const float* w4t, const float* scales, float* lds, const float* xvl,
-                                             int tid, int lane, int c, int hh, f32x16 (&yT)[4], MidHook mid_hook, bool center, float* zref PROF_ARGS) {
-    // ACT_SCALE: the node rows and the Swish output enter the split GEMMs multiplied by 2^6, so that the fp16 low halves of small
-    // activations stay normal (see tile_kernels.hip); every factor is a power of two folded into an existing constant.
-    const float sc3 = uniform_ro(scales, 2) * TAIL_NODE_SCALE, inv3 = uniform_ro(scales, 6) * (TAIL_ACT_SCALE / TAIL_NODE_SCALE), sc4 = uniform_ro(scales, 3) * TAIL_ACT_SCALE;
-    // Weight chunks reach LDS by LDS-DMA (round 4; the staged image is lane-linear, i.e. exactly what global_load_lds_dwordx4 writes):
-    // no register round trip (16 VGPRs, 4 ds_write_b128 per thread and chunk); a chunk is requested into the buffer the PREVIOUS
-    // chunk's MFMAs read, free since the barrier that ended that iteration, and the barrier at the end of this one waits for it.
-    wstage_dma(w3s, lds, tid);
-    float xv[8];
-    half8 wvf[2][4];
-    f32x16 z[4][1];
-    // acc_init_bias_scaled<1>(b3, sc3, hh, z) with all sixteen 16-byte loads in flight at once, INTO the accumulator registers (pinned
-    // there by the empty asm), scaled in place: left to the compiler they went through one four-register temporary, four round trips
-    // to L2 one after the other at the head of every update head (the phase profile's 3.7 k cycles of "head prologue")
+// update_net_1's bias into the accumulator registers: acc_init_bias_scaled<1>(b3, sc3, hh, z) with all sixteen 16-byte loads in flight at
+// once (tail_bias_load), pinned there by the empty asm and scaled in place (tail_bias_scale): left to the compiler they went through one
+// four-register temporary, four round trips to L2 one after the other at the head of every update head (the phase profile's 3.7 k cycles
+// of "head prologue").  The gated kernel loads BOTH heads' batches before it pins either.
+__device__ __forceinline__ void tail_bias_load(const float* b3, int hh, f32x16 (&z)[4][1]) {
 #pragma unroll
     for (int T = 0; T < 4; ++T)
 #pragma unroll
@@ -1045,34 +1034,53 @@ __device__ __forceinline__ void head_compute(float* rowbuf, int n0, int n1, cons
 #pragma unroll
             for (int m = 0; m < 4; ++m) z[T][0][4 * q + m] = bv[m];
         }
+}
+__device__ __forceinline__ void tail_bias_pin(f32x16 (&z)[4][1]) {
 #pragma unroll
     for (int T = 0; T < 4; ++T) asm volatile("" : "+v"(z[T][0]));
+}
+__device__ __forceinline__ void tail_bias_scale(f32x16 (&z)[4][1], float sc3) {
 #pragma unroll
     for (int T = 0; T < 4; ++T)
 #pragma unroll
         for (int r = 0; r < 16; ++r) z[T][0][r] *= sc3;
-    __syncthreads();                // (with the vmcnt(0) of the LDS-DMA in flight: chunk 0 of the rows has landed)
-    PROF_MARK(5);
-    const int myrow = (tid >> 6) * 32 + c;
+}
+// ACT_SCALE: the node rows and the Swish output enter the split GEMMs multiplied by 2^6, so that the fp16 low halves of small
+// activations stay normal (see tile_kernels.hip); every factor is a power of two folded into an existing constant.
+__device__ __forceinline__ float tail_sc3(const float* scales) { return uniform_ro(scales, 2) * TAIL_NODE_SCALE; }
+
+// this lane's B fragments of the staged 32-column chunk of its node row: ONE ds_read of the row and ONE fp16 split, whichever heads consume it
+__device__ __forceinline__ void tail_chunk_frags(const float* buf, int myrow, int hh, half8 (&bhi)[1][2], half8 (&blo)[1][2]) {
+    f32x4 pf[4];
+    tail_rows_read(buf, myrow, hh, pf);
 #pragma unroll
-    for (int ch = 0; ch < 8; ++ch) {
+    for (int s = 0; s < 2; ++s) {
+        const f32x4 v0 = pf[2 * s], v1 = pf[2 * s + 1];
+        // hi = fp16(256 x), lo = fp16(256 x - hi) as four mixed-precision FMAs per pair (split_node_pair; no clamp: |x| >= 256 becomes
+        // an fp16 infinity, the norm's statistics are not finite and the status word is raised -- tile_kernels.hip).  Round 4 first
+        // measured this form as nondeterministic: the inline asm's results reached an MFMA in the next slot, which gfx950 does not
+        // interlock (profiles/r04N_mfma_operand_hazard.md); split8_node ends with the guard.
+        const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+        split8_node(v, bhi[0][s], blo[0][s]);
+    }
+}
+
+// Chunks CH0..7 of ONE head's update_net_1 (chunk ch < 4: columns 32 ch of h, else columns 32 (ch - 4) of the head's aggregate): rows of chunk
+// CH0 requested into rowbuf[CH0 & 1] and weight chunk CH0 into lds[CH0 & 1] by the caller, both behind a barrier.  Weight chunks reach LDS by
+// LDS-DMA (round 4; the staged image is lane-linear, i.e. exactly what global_load_lds_dwordx4 writes): no register round trip (16 VGPRs,
+// 4 ds_write_b128 per thread and chunk); a chunk is requested into the buffer the PREVIOUS chunk's MFMAs read, free since the barrier that
+// ended that iteration, and the barrier at the end of this one waits for it.  Ends with the head's first w4t chunk in lds[0], behind a barrier.
+// PB: first of the three MSMP_PROF slots of this phase.
+template <int CH0, int PB>
+__device__ __forceinline__ void head_chunks(float* rowbuf, int n0, int n1, const float* __restrict__ h, const float* __restrict__ agg, const float* w3vh,
+                                            const float* w3s, const float* w4t, float* lds, int tid, int lane, int myrow, int hh, f32x16 (&z)[4][1],
+                                            half8 (&wvf)[2][4] PROF_ARGS) {
+#pragma unroll
+    for (int ch = CH0; ch < 8; ++ch) {
         if (ch < 7) tail_rows_issue(h, agg, n0, n1, ch + 1, rowbuf + ((ch + 1) & 1) * ROWBUF_FLOATS, tid);
         wstage_dma(ch < 7 ? w3s + (size_t)(ch + 1) * SPLIT_CHUNK_FLOATS : w4t, lds + ((ch + 1) & 1) * SPLIT_CHUNK_FLOATS, tid);
         half8 bhi[1][2], blo[1][2];
-        {
-            f32x4 pf[4];
-            tail_rows_read(rowbuf + (ch & 1) * ROWBUF_FLOATS, myrow, hh, pf);
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const f32x4 v0 = pf[2 * s], v1 = pf[2 * s + 1];
-                // hi = fp16(256 x), lo = fp16(256 x - hi) as four mixed-precision FMAs per pair (split_node_pair; no clamp: |x| >= 256 becomes
-                // an fp16 infinity, the norm's statistics are not finite and the status word is raised -- tile_kernels.hip).  Round 4 first
-                // measured this form as nondeterministic: the inline asm's results reached an MFMA in the next slot, which gfx950 does not
-                // interlock (profiles/r04N_mfma_operand_hazard.md); split8_node ends with the guard.
-                const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-                split8_node(v, bhi[0][s], blo[0][s]);
-            }
-        }
+        tail_chunk_frags(rowbuf + (ch & 1) * ROWBUF_FLOATS, myrow, hh, bhi, blo);
         if (ch == 5) {      // the variables' slot fragments are consumed after the k loop: issued two chunks ahead
             const half8* wv = reinterpret_cast<const half8*>(w3vh) + lane;
 #pragma unroll
@@ -1080,30 +1088,40 @@ __device__ __forceinline__ void head_compute(float* rowbuf, int n0, int n1, cons
 #pragma unroll
                 for (int T = 0; T < 4; ++T) wvf[m][T] = wv[(m * 4 + T) * 64];
         }
-        PROF_MARK(6);
+        PROF_MARK(PB);
         mma_chunk_split<1>(lds + (ch & 1) * SPLIT_CHUNK_FLOATS, lane, bhi, blo, z);
-        PROF_MARK(7);
-        PROF_MARK(8);
+        PROF_MARK(PB + 1);
         __syncthreads();
-        PROF_MARK(9);
+        PROF_MARK(PB + 2);
     }
-    {
-        half8 bx[2];
-        // the node's variables from the LDS table the kernel filled at its start (as `f < nv ? vars[...] : 0` inside the chunk loop every
-        // load sat in a branch of its own with a wait right behind it: up to eight exposed round trips per head)
-        const f32x4 x0 = *reinterpret_cast<const f32x4*>(xvl + 8 * myrow), x1 = *reinterpret_cast<const f32x4*>(xvl + 8 * myrow + 4);
-        const float xr[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
+}
+
+// the variables' slot fragments of this lane's node (they depend on the node only: the gated kernel makes them once for both heads)
+__device__ __forceinline__ void tail_var_frags(const float* xvl, int myrow, int hh, half8 (&bx)[2]) {
+    // the node's variables from the LDS table the kernel filled at its start (as `f < nv ? vars[...] : 0` inside the chunk loop every
+    // load sat in a branch of its own with a wait right behind it: up to eight exposed round trips per head)
+    const f32x4 x0 = *reinterpret_cast<const f32x4*>(xvl + 8 * myrow), x1 = *reinterpret_cast<const f32x4*>(xvl + 8 * myrow + 4);
+    const float xr[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
+    float xv[8];
 #pragma unroll
-        for (int f = 0; f < 8; ++f) xv[f] = tail_node_scaled(xr[f]);
-        var_slot_frags(xv, hh, bx);
+    for (int f = 0; f < 8; ++f) xv[f] = tail_node_scaled(xr[f]);
+    var_slot_frags(xv, hh, bx);
+}
+
+// The rest of one head behind its eight chunks: the variables' columns, Swish, centring, update_net_2 (transposed).  mid_hook runs where the
+// row registers are free (the gated kernel requests the main head's first aggregate chunk there), last_hook at the top of update_net_2's
+// last chunk, where lds[0] is free (the main head's next weight chunk).
+template <typename MidHook, typename LastHook>
+__device__ __forceinline__ void head_finish(const float* b4, const float* w4t, const float* scales, float* lds, int tid, int lane, int c, int hh,
+                                            f32x16 (&z)[4][1], const half8 (&wvf)[2][4], const half8 (&bx)[2], f32x16 (&yT)[4], MidHook mid_hook,
+                                            LastHook last_hook, bool center, float* zref) {
+    const float inv3 = uniform_ro(scales, 6) * (TAIL_ACT_SCALE / TAIL_NODE_SCALE), sc4 = uniform_ro(scales, 3) * TAIL_ACT_SCALE;
 #pragma unroll
-        for (int m = 0; m < 2; ++m)
+    for (int m = 0; m < 2; ++m)
 #pragma unroll
-            for (int T = 0; T < 4; ++T) z[T][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wvf[m][T], bx[m], z[T][0], 0, 0, 0);
-    }
+        for (int T = 0; T < 4; ++T) z[T][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wvf[m][T], bx[m], z[T][0], 0, 0, 0);
     mid_hook();             // the row registers are free from here on
     __builtin_amdgcn_sched_barrier(0);      // (the requests stay HERE: sunk to the barrier below, its fence waits for them where they are issued)
-    PROF_MARK(10);
 #pragma unroll
     for (int T = 0; T < 4; ++T)
 #pragma unroll
@@ -1151,6 +1169,7 @@ __device__ __forceinline__ void head_compute(float* rowbuf, int n0, int n1, cons
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         if (t < 3) wstage_dma(w4t + (size_t)(t + 1) * SPLIT_CHUNK_FLOATS, lds + ((t + 1) & 1) * SPLIT_CHUNK_FLOATS, tid);
+        else last_hook();
         __builtin_amdgcn_sched_barrier(0);  // (as above: the next chunk is requested at the top of the iteration, not in front of its barrier)
         half8 zhi[1][2], zlo[1][2];
         split_acc_tile<1>(z[t], zhi, zlo);
@@ -1250,8 +1269,6 @@ __global__ __launch_bounds__(256, 2) void node_tail_split_kernel(TailArgs a) {
     const int n0 = a.graph_ptr[blockIdx.x], n1 = a.graph_ptr[blockIdx.x + 1];
     const int cnt = n1 - n0;
     if (cnt <= 0) return;
-    const long n = (long)n0 + wave * 32 + c;
-    const long nc = n < n1 ? n : n1 - 1;
 
     PROF_DECL
 #pragma unroll
@@ -1260,24 +1277,73 @@ __global__ __launch_bounds__(256, 2) void node_tail_split_kernel(TailArgs a) {
         const float v = a.vars[(size_t)min(n0 + row, n1 - 1) * a.nv + min(f, a.nv - 1)];
         xvl[e] = v * (row < cnt && f < a.nv ? 1.0f : 0.f);        // (a product, not a select of the loaded value: the compiler turns that into a branch around the load, with the wait behind it)
     }
-    f32x16 tau[4];
+    const int myrow = wave * 32 + c;
+    f32x16 tau[4], y[4];
+    f32x16 z[4][1];             // the main head's update_net_1 accumulator
+    half8 wvf[2][4], bx[2];
     if (GATED) {
+        // h enters update_net_1 of BOTH heads from one staging and one fp16 split per chunk: over chunks 0..3 every row chunk feeds two
+        // weight stages (even: the gate head's W3 chunk into zg, odd: the main head's into z), the weight chunks alternating through the two
+        // buffers as before.  Each head's accumulation order is what it was (bias, h chunks, aggregate chunks, variables): the same bits.
+        // The gate head then finishes (its aggregate chunks .. tau) with the main head's partial sums parked in z.
+        f32x16 zg[4][1];
         tail_rows_issue(a.h, a.agg[1], n0, n1, 0, rowbuf, tid);
-        head_compute(rowbuf, n0, n1, a.h, a.agg[1], a.vars, nc, a.nv, a.b3[1], a.b4[1], a.w3vh[1], a.w3s[1], a.w4t[1], a.scales[1], lds, xvl, tid, lane,
-                     c, hh, tau, [&] { tail_rows_issue(a.h, a.agg[0], n0, n1, 0, rowbuf, tid); }, true, tot PROF_PASS);
+        wstage_dma(a.w3s[1], lds, tid);
+        tail_bias_load(a.b3[1], hh, zg);            // ONE prologue: both heads' bias batches in flight together, ahead of the first barrier
+        tail_bias_load(a.b3[0], hh, z);
+        tail_bias_pin(zg);
+        tail_bias_pin(z);
+        tail_bias_scale(zg, tail_sc3(a.scales[1]));
+        tail_bias_scale(z, tail_sc3(a.scales[0]));
+        __syncthreads();                // (with the vmcnt(0) of the LDS-DMA in flight: chunk 0 of the rows has landed)
+        PROF_MARK(5);
+        half8 bhi[1][2], blo[1][2];
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+            const int ch = s >> 1;
+            if (!(s & 1)) {
+                tail_rows_issue(a.h, a.agg[1], n0, n1, ch + 1, rowbuf + ((ch + 1) & 1) * ROWBUF_FLOATS, tid);      // (chunk 4: the gate head's aggregate)
+                wstage_dma(a.w3s[0] + (size_t)ch * SPLIT_CHUNK_FLOATS, lds + SPLIT_CHUNK_FLOATS, tid);
+                __builtin_amdgcn_sched_barrier(0);      // (the requests stay HERE, as in head_finish)
+                tail_chunk_frags(rowbuf + (ch & 1) * ROWBUF_FLOATS, myrow, hh, bhi, blo);
+                PROF_MARK(6);
+                mma_chunk_split<1>(lds, lane, bhi, blo, zg);
+            } else {
+                wstage_dma(a.w3s[1] + (size_t)(ch + 1) * SPLIT_CHUNK_FLOATS, lds, tid);
+                __builtin_amdgcn_sched_barrier(0);
+                PROF_MARK(6);
+                mma_chunk_split<1>(lds + SPLIT_CHUNK_FLOATS, lane, bhi, blo, z);
+            }
+            PROF_MARK(7);
+            __syncthreads();
+            PROF_MARK(8);
+        }
+        head_chunks<4, 9>(rowbuf, n0, n1, a.h, a.agg[1], a.w3vh[1], a.w3s[1], a.w4t[1], lds, tid, lane, myrow, hh, zg, wvf PROF_PASS);
+        tail_var_frags(xvl, myrow, hh, bx);
+        head_finish(a.b4[1], a.w4t[1], a.scales[1], lds, tid, lane, c, hh, zg, wvf, bx, tau,
+                    [&] { tail_rows_issue(a.h, a.agg[0], n0, n1, 4, rowbuf, tid); },
+                    [&] { wstage_dma(a.w3s[0] + (size_t)4 * SPLIT_CHUNK_FLOATS, lds, tid); }, true, tot);
         PROF_MARK(0);
         tile_t_instance_norm(tau, wave, cnt, uniform_ro(a.scales[1], 7) * (1.0f / TAIL_ACT_SCALE), a.eps, part, tot, tid, c, hh, a.status);
 #pragma unroll
         for (int T = 0; T < 4; ++T)
 #pragma unroll
             for (int r = 0; r < 16; ++r) tau[T][r] = sigmoidf_(tau[T][r]);
+        __syncthreads();                // (the main head's aggregate rows and weight chunk 4, requested inside head_finish, have landed in every wave)
         PROF_MARK(1);
+        head_chunks<4, 12>(rowbuf, n0, n1, a.h, a.agg[0], a.w3vh[0], a.w3s[0], a.w4t[0], lds, tid, lane, myrow, hh, z, wvf PROF_PASS);
     } else {
         tail_rows_issue(a.h, a.agg[0], n0, n1, 0, rowbuf, tid);
+        wstage_dma(a.w3s[0], lds, tid);
+        tail_bias_load(a.b3[0], hh, z);
+        tail_bias_pin(z);
+        tail_bias_scale(z, tail_sc3(a.scales[0]));
+        __syncthreads();                // (with the vmcnt(0) of the LDS-DMA in flight: chunk 0 of the rows has landed)
+        PROF_MARK(5);
+        head_chunks<0, 12>(rowbuf, n0, n1, a.h, a.agg[0], a.w3vh[0], a.w3s[0], a.w4t[0], lds, tid, lane, myrow, hh, z, wvf PROF_PASS);
+        tail_var_frags(xvl, myrow, hh, bx);
     }
-    f32x16 y[4];
-    head_compute(rowbuf, n0, n1, a.h, a.agg[0], a.vars, nc, a.nv, a.b3[0], a.b4[0], a.w3vh[0], a.w3s[0], a.w4t[0], a.scales[0], lds, xvl, tid, lane, c, hh,
-                 y, [] {}, GATED || a.mode == MSMP_LAYER_LIN, tot PROF_PASS);
+    head_finish(a.b4[0], a.w4t[0], a.scales[0], lds, tid, lane, c, hh, z, wvf, bx, y, [] {}, [] {}, GATED || a.mode == MSMP_LAYER_LIN, tot);
     PROF_MARK(2);
     // this lane's piece of the transposed tiles: nodes n0 + 32 wave + acc_row(r, hh), channels 4 c .. 4 c + 3 (tile T = channel 4 c + T)
     const size_t base = ((size_t)n0 + wave * 32 + 4 * hh) * H + 4 * c;

@@ -18,7 +18,12 @@ with torch.no_grad():
     buf = (ctypes.c_ulonglong * 16)()
     L.msmp_debug_prof(buf, 0)
     n = buf[15] or 1        # workgroups that reported (one in 16)
-    names = ['gate head rest (GEMM4)', 'gate norm+sigmoid', 'main head rest', 'main norm', 'blend+store', 'head prologue (x2)', 'chunk: split+rowload (x16)', 'chunk: mma (x16)', 'chunk: weight wait+store (x16)', 'chunk: barrier (x16)', 'swish z (x2)']
-    tot = sum(buf[i] for i in range(11))
+    # the gated tail's phases (mlp_kernels.hip, PROF_MARK): ONE prologue for both heads, the four h chunks staged and split once and
+    # multiplied against both heads' W3 chunks (8 weight stages), then each head's four aggregate chunks and its rest
+    names = ['gate head rest (variables, Swish, GEMM4)', 'gate norm+sigmoid', 'main head rest (variables, Swish, GEMM4)', 'main norm', 'blend+store',
+             'prologue, both heads (x1)', 'shared h chunks: split+rowload (x4) / request (x8)', 'shared h chunks: mma (x8)', 'shared h chunks: barrier (x8)',
+             'gate agg chunks: split+rowload (x4)', 'gate agg chunks: mma (x4)', 'gate agg chunks: barrier (x4)',
+             'main agg chunks: split+rowload (x4)', 'main agg chunks: mma (x4)', 'main agg chunks: barrier (x4)']
+    tot = sum(buf[i] for i in range(15))
     print(f'node_tail_split_kernel: {tot / n:.0f} cycles per workgroup (wave 0)')
-    for i, nm in enumerate(names): print(f'  {nm:32s} {buf[i] / n:10.0f} cycles  {100.0 * buf[i] / tot:5.1f} %')
+    for i, nm in enumerate(names): print(f'  {nm:52s} {buf[i] / n:10.0f} cycles  {100.0 * buf[i] / tot:5.1f} %')
