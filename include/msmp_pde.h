@@ -413,8 +413,9 @@ int msmp_lem_train_bwd_f32(const float* grad_y, const float* saved, const float*
  * layer (what torch.autograd produces over experiments/models_gnn.py:61-149 and the blend :1204-1207).  params_* / grads_*:
  * arrays of 8 device pointers in the order message_net_1.0.weight, .bias, message_net_2.0.weight, .bias, update_net_1.0.weight,
  * .bias, update_net_2.0.weight, .bias, in the reference's [out, in] layouts (NOT the packed blobs); gate arrays NULL for a
- * single layer.  u, pos, vars carry no gradient.  GEMMs with edge- / node-sized outputs run on rocBLAS (looked up in the
- * process at run time: MSMP_ERR_UNSUPPORTED if librocblas cannot be loaded).  src_rowptr [N+1] / src_perm [E] (both or
+ * single layer.  u, pos, vars carry no gradient.  GEMMs with edge- / node-sized outputs run on the library's own bf16x3 row-GEMM
+ * kernels at every size; only with msmp_tune("bwd_gemm", 0) do they go to rocblas_sgemm, which is then looked up in the process
+ * at run time (MSMP_ERR_UNSUPPORTED if librocblas cannot be loaded; never loaded otherwise).  src_rowptr [N+1] / src_perm [E] (both or
  * neither): the CSR edge ids regrouped by SOURCE node, ascending inside a source; with them dh's source-side scatter runs in
  * that fixed order (bitwise reproducible gradients), without them it uses float atomics.  tw + 1 + nv <= 128; above 64 (2-D windows
  * of 50) only with src_rowptr / src_perm and the own GEMMs (tune "bwd_gemm" != 0), else MSMP_ERR_UNSUPPORTED.

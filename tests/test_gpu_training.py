@@ -328,8 +328,9 @@ def test_grad_weights_kernel_shapes_and_strides(mp):
 
 @pytest.fixture(params=[0, 2], ids=['rocblas', 'own_gemm'])
 def bwd_gemm(request, mp):
-    """Both GEMM paths of msmp_mp_layer_bwd_f32 (tune "bwd_gemm": 0 = rocblas_sgemm + separate epilogues, 2 = rows_gemm_kernel; the
-    default picks by size, which at test sizes would always be the library)."""
+    """Both GEMM paths of msmp_mp_layer_bwd_f32 (tune "bwd_gemm": 0 = rocblas_sgemm + separate epilogues, kept for A/B runs;
+    any other value, the default 1 included, = the library's own row GEMMs at every size: rows_gemm_small_kernel below 32 768
+    rows, which is where these tests are, rows_gemm_kernel from there on: test_gpu_backward_sizes.py)."""
     from msmp_pde_amd._lib import check
     L = mp.lib()
     prev = L.msmp_tune_query(b'bwd_gemm')
