@@ -89,6 +89,8 @@ int msmp_last_status(int* flags_out, int reset);
  *   "lem_share" k (default 1): k LEM launches share the GPU (sub-batches on k streams): each plans its rounds for CUs / k.
  *   "lem_tail" 1 (default): the LEM launch ends with a round of one-tile workgroups where that saves >= 0.3 of a round; 0: three-tile
  *             workgroups only (same bits either way).
+ *   "lem_wide" 1 (default): the host's no-grad LEM at widths other than 128 is one msmp_lem_encoder_wide_f32 launch; 0: the loop of two
+ *             library GEMMs + msmp_wide_lem_z_f32 / _y_f32 per time step (the entry itself does not read the key).
  *   "tile_arith" 1 (default): ranged tiles take their node rows by arithmetic on tile_halo; 0: always through the node list.
  *   "tail"    1 (default): msmp_mp_layer_f32 uses msmp_node_tail_f32 for graphs of up to 128 nodes; 0: the piecewise kernels.
  *   "pair"    gated pair: both heads' projection / message kernels in one launch each (bit-identical results): 0 never,
@@ -519,6 +521,18 @@ int msmp_wide_swish_f32(const float* x, int64_t n_floats, float* out, msmp_strea
  * z <- (1 - dt sigmoid(g2)) z + dt sigmoid(g2) tanh(g3);  then with lin [N, width] = [z, x_t] Wz^T + bz:  y <- (1 - dtbar) y + dtbar tanh(lin). */
 int msmp_wide_lem_z_f32(const float* g, int64_t n_nodes, int width, float dt, float* z, float* dtbar_out, msmp_stream_t stream);
 int msmp_wide_lem_y_f32(const float* lin, const float* dtbar, int64_t n_floats, float* y, msmp_stream_t stream);
+/* The whole T-step recurrence of that cell at any hidden width 1 <= width <= 256 in ONE launch (LEMcuda.forward / LEMFunction.forward,
+ * experiments/models_gnn.py:285-342): fp16-split MFMA arithmetic of the default path, weights streamed from L2, states in registers and LDS.
+ * Blob size / pack: weights [3 width, width + ninp], weights_lin_z [width, width + ninp], bias [3 width], bias_lin_z [width]; ninp 1..8. */
+int64_t msmp_packed_lem_wide_floats(int ninp, int width);      /* 0 (and msmp_last_error) for a width or ninp outside the range */
+int msmp_pack_lem_wide_f32(const float* weights, const float* weights_lin_z, const float* bias, const float* bias_lin_z, int ninp, int width,
+                           float* packed_out, msmp_stream_t stream);
+/* experiments/models_gnn.py:285-342: xin [n_nodes, t_len, msmp_lem_input_stride(ninp)] (node-major step inputs, as msmp_lem_encoder_f32),
+ * y0 / z0 [n_nodes, width] the initial states (`states`, :325-332; both NULL = zeros) -> y_out = all_y[-1], z_out = all_z[-1] (or NULL),
+ * dense [n_nodes, width].  MSMP_ERR_UNSUPPORTED for width outside 1..256 or ninp outside 1..8, MSMP_ERR_ARG for t_len < 1 or a null
+ * required pointer; n_nodes = 0 is a no-op.  A step input with |x| > 255 or not finite raises MSMP_STATUS_INPUT_RANGE. */
+int msmp_lem_encoder_wide_f32(const float* xin, int64_t n_nodes, int t_len, int ninp, int width, float dt, const float* packed,
+                              const float* y0, const float* z0, float* y_out, float* z_out, msmp_stream_t stream);
 /* gate_pre == NULL: out = InstanceNorm(main_pre); else out = (1 - tau) h + tau Swish(IN(main_pre)), tau = sigmoid(IN(gate_pre)) */
 int msmp_wide_norm_blend_f32(const float* h, const float* gate_pre, const float* main_pre, const int32_t* graph_ptr, int64_t n_graphs,
                              int width, int ld, float eps, float* out, msmp_stream_t stream);

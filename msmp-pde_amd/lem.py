@@ -27,7 +27,41 @@ class LEMcuda(nn.Module):
         self.weights_lin_z = nn.Parameter(torch.empty(nhid, ninp + nhid, dtype=torch.float32))
         self.bias = nn.Parameter(torch.empty(3 * nhid, dtype=torch.float32))
         self.bias_lin_z = nn.Parameter(torch.empty(nhid, dtype=torch.float32))
+        self._wide_blob = None
+        self._wide_key = None
         self.reset_parameters()
+
+    def _pack_wide(self):
+        """The blob of msmp_lem_encoder_wide_f32, cached like LEM._pack: parameter addresses, versions and PARAM_EPOCH."""
+        ps = [self.weights, self.weights_lin_z, self.bias, self.bias_lin_z]
+        key = (PARAM_EPOCH[0],) + tuple((p.data_ptr(), p._version, str(p.device)) for p in ps)
+        if key != self._wide_key:
+            L = lib()
+            n_floats = L.msmp_packed_lem_wide_floats(self.ninp, self.nhid)
+            if n_floats <= 0:
+                check(MSMP_ERR_UNSUPPORTED, 'msmp_packed_lem_wide_floats')
+            blob = torch.empty(n_floats, dtype=torch.float32, device=ps[0].device)
+            f = [p.detach().to(torch.float32).contiguous() for p in ps]
+            check(L.msmp_pack_lem_wide_f32(*[ptr(t) for t in f], self.ninp, self.nhid, ptr(blob), current_stream()), 'msmp_pack_lem_wide_f32')
+            self._wide_blob, self._wide_key = blob, key
+        return self._wide_blob
+
+    def wide_kernel_selected(self):
+        """True where a no-grad fp32 CUDA forward is ONE msmp_lem_encoder_wide_f32 launch: msmp_tune "lem_wide" and "split" both on
+        (the exact-fp32 path, `_lib.exact_fp32()`, keeps the GEMM + pointwise loop: Solver.range_policy falls back to it)."""
+        L = lib()
+        return bool(L.msmp_tune_query(b'lem_wide')) and bool(L.msmp_tune_query(b'split')) and 1 <= self.ninp <= 8 and 1 <= self.nhid <= 256
+
+    def forward_wide(self, xin, states=None):
+        """xin [N, T, ninp] node-major fp32 CUDA, states (y0, z0) or None -> (y_T, z_T) on the width-generic HIP recurrence kernel."""
+        x = _padded_inputs(xin)
+        n, t_len = x.shape[0], x.shape[1]
+        y0, z0 = (None, None) if states is None else (_state(states[0]), _state(states[1]))
+        y = torch.empty(n, self.nhid, dtype=torch.float32, device=x.device)
+        z = torch.empty_like(y)
+        check(lib().msmp_lem_encoder_wide_f32(ptr(x), n, t_len, self.ninp, self.nhid, self.dt, ptr(self._pack_wide()), ptr(y0), ptr(z0),
+                                              ptr(y), ptr(z), current_stream()), 'msmp_lem_encoder_wide_f32')
+        return y, z
 
     def reset_parameters(self):
         stdv = 1.0 / math.sqrt(self.nhid)
@@ -39,15 +73,19 @@ class LEMcuda(nn.Module):
         (models_gnn.py:325-332), default zeros."""
         t_len, n, _ = inputs.shape
         nh = self.nhid
+        infer = inputs.is_cuda and inputs.dtype == torch.float32 and not torch.is_grad_enabled()
+        if infer and n > 0 and self.wide_kernel_selected():      # inference at any width (the GLU classes): one launch for all T steps
+            y, z = self.forward_wide(inputs.permute(1, 0, 2), states)
+            return (y, z) if return_state else y
         y, z = (inputs.new_zeros(n, nh), inputs.new_zeros(n, nh)) if states is None else states
         wy, wx = self.weights[:, :nh].t().contiguous(), self.weights[:, nh:].t().contiguous()
         zy, zx = self.weights_lin_z[:, :nh].t().contiguous(), self.weights_lin_z[:, nh:].t().contiguous()
         # input projections for all steps at once (the recurrent part stays sequential)
         gx = torch.matmul(inputs, wx) + self.bias          # [T, N, 3H]
         lx = torch.matmul(inputs, zx) + self.bias_lin_z    # [T, N, H]
-        if inputs.is_cuda and inputs.dtype == torch.float32 and not torch.is_grad_enabled():
-            # inference at any width (the GLU classes): the two recurrent GEMMs stay library calls, the pointwise work between them is one
-            # HIP launch each (msmp_wide_lem_z_f32 / _y_f32) instead of ~20 elementwise kernels per time step
+        if infer:
+            # msmp_tune("lem_wide", 0) / the exact-fp32 path: the two recurrent GEMMs are library calls, the pointwise work between them is
+            # one HIP launch each (msmp_wide_lem_z_f32 / _y_f32)
             L = lib()
             y, z = y.contiguous().clone(), z.contiguous().clone()
             dt_bar = torch.empty_like(y)
@@ -155,7 +193,9 @@ class LEM(nn.Module):
         """Same with node-major step inputs xin [N, T, ninp] (the layout the kernels read)."""
         if not xin.is_cuda:
             raise RuntimeError('LEM needs CUDA tensors; there is no CPU fallback')
-        if self.nhid != 128:            # the GLU classes (164 hidden units): the PyTorch-ROCm restatement of the cell (north_star keeps the encoder in PyTorch)
+        if self.nhid != 128:            # the GLU classes (164 hidden units): no grad = the width-generic HIP kernel, else the PyTorch-ROCm restatement of the cell
+            if not torch.is_grad_enabled() and xin.shape[0] > 0 and self.rnn.weights.dtype == torch.float32 and self.rnn.wide_kernel_selected():
+                return self.rnn.forward_wide(xin)[0]
             return self.rnn(xin.permute(1, 0, 2).contiguous().to(self.rnn.weights.dtype))
         if not self.TRAIN_KERNELS:
             return self.rnn(xin.permute(1, 0, 2).contiguous())
@@ -211,8 +251,10 @@ class LEM(nn.Module):
 class LEMS(LEM):
     """experiments/models_gnn.py:345-362: the LEM that keeps (all_y[-1], all_z[-1]) of a call as the initial states of the next
     (`reset_states()` starts a new unrolling sequence; train_helper.py:144-145, 199-200).  The carried states are constants for
-    the next call.  Runs on the exact-fp32 recurrence kernel (msmp_lem_train_fwd_f32; with autograd its BPTT pair), which takes
-    initial states; the weight-stationary inference kernel starts from zeros and is not used here."""
+    the next call.  At width 128 it runs on the exact-fp32 recurrence kernel (msmp_lem_train_fwd_f32; with autograd its BPTT pair), which
+    takes initial states; the weight-stationary inference kernel starts from zeros and is not used here.  At any other width: without
+    grad LEMcuda.forward's inference branch (msmp_lem_encoder_wide_f32, or the GEMM loop under msmp_tune "lem_wide" 0 / exact fp32), with
+    grad the PyTorch-ROCm restatement, both with the carried states."""
 
     def __init__(self, ninp, nhid, dt=1.):
         super().__init__(ninp, nhid, dt)
@@ -227,9 +269,11 @@ class LEMS(LEM):
     def forward_nodes(self, xin):
         y0, z0 = self.states if self.states is not None else (None, None)
         r = self.rnn
-        if not (xin.is_cuda and self.nhid == 128):
+        if not xin.is_cuda:
             raise RuntimeError('LEMS needs CUDA tensors (HIP path only, no CPU fallback)')
-        if torch.is_grad_enabled() and any(p.requires_grad for p in r.parameters()):
+        if self.nhid != 128:
+            y, z = r(xin.permute(1, 0, 2).contiguous().to(r.weights.dtype), None if y0 is None else (y0, z0), return_state=True)
+        elif torch.is_grad_enabled() and any(p.requires_grad for p in r.parameters()):
             if self.TRAIN_KERNELS:
                 y, z = _LEMTrainFunction.apply(self, xin, r.weights, r.weights_lin_z, r.bias, r.bias_lin_z, y0, z0)
             else:

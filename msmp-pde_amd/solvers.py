@@ -260,8 +260,11 @@ class _SolverBase(nn.Module):
             return self._embed_hip(u, pos_x, variables)
         if isinstance(self.embedding_lem, LEMS):       # stateful encoder: always the state-taking recurrence kernel
             return self.lemoutput_mlp(self.embedding_lem.forward_nodes(self._step_inputs(u, pos_x, pos_t, variables, dt)))
-        if self.hidden_features != 128:     # the GLU classes: LEM cell and lemoutput_mlp as PyTorch-ROCm ops (any width; lem.LEM.forward_nodes)
-            return self.lemoutput_mlp(self.embedding_lem.forward_nodes(self._step_inputs(u, pos_x, pos_t, variables, dt)))
+        if self.hidden_features != 128:     # the GLU classes (any width; lem.LEM.forward_nodes): no grad = the width-generic HIP recurrence + two HIP row GEMMs
+            y = self.embedding_lem.forward_nodes(self._step_inputs(u, pos_x, pos_t, variables, dt))
+            if not torch.is_grad_enabled() and y.dtype == torch.float32 and self.embedding_lem.rnn.wide_kernel_selected():
+                return self._lemoutput_mlp_hip(y)
+            return self.lemoutput_mlp(y)
         grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.embedding_lem.parameters())
         if not grad:                    # step inputs assembled inside the kernel (no [N, T, ninp] tensor)
             h = self.embedding_lem.encode_nodes(u, pos_x, pos_t, variables, dt, self.TWO_D, self.lemoutput_mlp)
@@ -272,6 +275,23 @@ class _SolverBase(nn.Module):
             h = self.embedding_lem.forward_nodes(lem_in)       # HIP training kernels (recurrence forward + BPTT)
             return self.lemoutput_mlp(h)
         return self.embedding_lem.encode(lem_in, self.lemoutput_mlp)       # fused HIP kernel (recurrence + MLP)
+
+    def _lemoutput_mlp_hip(self, y):
+        """lemoutput_mlp (models_gnn.py:1287-1291: Linear + Swish + Linear + Swish) at a width other than 128 as two msmp_linear_f32
+        calls with the bias + Swish epilogue (mode 1)."""
+        from .layers import _wide_linear, _Workspace
+        W, n = self.hidden_features, y.shape[0]
+        ld = 128 * ((W + 127) // 128)
+        x = torch.nn.functional.pad(y, (0, (-W) % 4)).contiguous()
+        w = [p.detach().to(torch.float32).contiguous() for p in (self.lemoutput_mlp[0].weight, self.lemoutput_mlp[0].bias,
+                                                                   self.lemoutput_mlp[2].weight, self.lemoutput_mlp[2].bias)]
+        ws = _Workspace.get(lib().msmp_linear_workspace_bytes(W, W), y.device)
+        a = torch.empty(n, ld, dtype=torch.float32, device=y.device)
+        b = torch.empty(n, ld, dtype=torch.float32, device=y.device)
+        _wide_linear(x, W, w[0], w[1], W, 1, a, ws)
+        _wide_linear(a, W, w[2], w[3], W, 1, b, ws)
+        b._msmp_keep = w            # the kernels read the weights after this returns
+        return b[:, :W].contiguous()
 
     def _step_inputs(self, u, pos_x, pos_t, variables, dt):
         """The recurrent encoder's per-step inputs, node-major [N, T, ninp]."""
@@ -674,7 +694,8 @@ class _GLUBase(_SolverBase):
     gated pair of CNNs on the two halves of the hidden state,  out = (1 - scale) u_last + cumsum(dt) scale diff  with
     scale = output_mlp_gate(h[..., :82]), diff = output_mlp_diff(h[..., 82:])  (experiments/models_gnn.py:1379-1523,
     models_gnn2D.py:1198-1366; no sigmoid on `scale`, as in the reference).  Layers: the width-generic HIP path
-    (layers._mp_layer_wide); LEM cell, lemoutput_mlp, double_mlp and the two small CNNs: PyTorch-ROCm ops."""
+    (layers._mp_layer_wide); without grad the LEM recurrence is one HIP launch (msmp_lem_encoder_wide_f32) and lemoutput_mlp two HIP row
+    GEMMs; double_mlp and the two small CNNs: PyTorch-ROCm ops."""
     GATED, LEM_ENCODER, LAYER = True, True, GNN_LayerLin
 
     def __init__(self, pde, time_window=25, hidden_features=164, hidden_layer=6, eq_variables={}, save_state=None):
