@@ -91,12 +91,16 @@ int msmp_last_status(int* flags_out, int reset);
  *             workgroups only (same bits either way).
  *   "lem_wide" 1 (default): the host's no-grad LEM at widths other than 128 is one msmp_lem_encoder_wide_f32 launch; 0: the loop of two
  *             library GEMMs + msmp_wide_lem_z_f32 / _y_f32 per time step (the entry itself does not read the key).
+ *   "wide_msg" 1 (default): the host's no-grad layer at widths other than 128 evaluates the message half of a head as one
+ *             msmp_wide_message_f32 launch; 0: msmp_wide_gather_swish_f32 + msmp_linear_f32 + msmp_wide_scatter_mean_f32 around two
+ *             [E, ld] tensors (the entry itself does not read the key).  The host takes the fused launch only while "split" and
+ *             "lem_wide" are 1 as well: "lem_wide" 0 selects the unfused width-generic path as a whole, bitwise the exact-fp32 evaluation.
  *   "tile_arith" 1 (default): ranged tiles take their node rows by arithmetic on tile_halo; 0: always through the node list.
  *   "tail"    1 (default): msmp_mp_layer_f32 uses msmp_node_tail_f32 for graphs of up to 128 nodes; 0: the piecewise kernels.
  *   "pair"    gated pair: both heads' projection / message kernels in one launch each (bit-identical results): 0 never,
  *             1 (default) for batches of up to 65 536 nodes, where a step is bound by the latency of its ~60 dependent launches, 2 always. */
 int msmp_tune(const char* key, int value);
-int msmp_tune_query(const char* key);      /* current value of "split", "tail", "pair", "bwd_gemm", "tile", "tile_arith" (0 for other keys) */
+int msmp_tune_query(const char* key);      /* current value of "split", "tail", "pair", "bwd_gemm", "tile", "tile_arith", "lem_wide", "wide_msg", ... (0 for unknown keys) */
 
 /* ---------------------------------------------------------------------------------------------
  * Weights
@@ -533,6 +537,25 @@ int msmp_pack_lem_wide_f32(const float* weights, const float* weights_lin_z, con
  * required pointer; n_nodes = 0 is a no-op.  A step input with |x| > 255 or not finite raises MSMP_STATUS_INPUT_RANGE. */
 int msmp_lem_encoder_wide_f32(const float* xin, int64_t n_nodes, int t_len, int ninp, int width, float dt, const float* packed,
                               const float* y0, const float* z0, float* y_out, float* z_out, msmp_stream_t stream);
+/* The message half of one head at any hidden width 1 <= width <= 256 in ONE launch, nothing edge-sized in memory
+ * (experiments/models_gnn.py:132-138 message with message_net_1 factorised per node into p / q, :107 aggr = 'mean'):
+ *   agg_out[n][c] = (1 / max(deg n, 1)) sum_{r in CSR row n} Swish(b2[c] + sum_k w2[c][k] Swish(p[n][k] + q[col[r]][k])),   c < width,
+ * summed in CSR order in fp32 (the result does not depend on the batch around a node); zero in-degree gives an exact 0; columns
+ * width .. ld - 1 of agg_out are written as 0 (as msmp_wide_scatter_mean_f32 writes them); p, q, agg_out [n_nodes, ld] with ld a
+ * multiple of 4 in width .. 4096, 16-byte aligned; columns width .. ld - 1 of p and q are not used.  fp16-split MFMA arithmetic of the
+ * default path with W2 in registers; an activation Swish(p + q) with |x| > 255 or not finite raises MSMP_STATUS_NODE_SATURATED.
+ * Blob size / pack (experiments/models_gnn.py:132-138: message_net_2[0].weight [width, width] and .bias; :107): 0 and msmp_last_error
+ * for a width outside 1..256. */
+int64_t msmp_packed_wide_msg_floats(int width);
+int msmp_pack_wide_msg_f32(const float* w2, const float* b2, int width, float* packed_out, msmp_stream_t stream);
+/* experiments/models_gnn.py:132-138, :107: the largest in-degree msmp_wide_message_f32 takes at this width (at least 32, the neighbour
+ * cap of the reference's radius graphs); 0 and msmp_last_error for a width outside 1..256. */
+int msmp_wide_message_max_in_degree(int width);
+/* experiments/models_gnn.py:132-138, :107.  max_in_degree: an upper bound of the in-degrees of rowptr (GraphStructure.max_in_degree);
+ * above msmp_wide_message_max_in_degree(width): MSMP_ERR_UNSUPPORTED (the caller takes the three launches above).  MSMP_ERR_ARG for a
+ * width outside 1..256, a bad ld, a null or misaligned pointer; n_nodes == 0 is a no-op, n_edges == 0 writes zeros. */
+int msmp_wide_message_f32(const float* p, const float* q, const int32_t* rowptr, const int32_t* col, int64_t n_nodes, int64_t n_edges,
+                          int max_in_degree, int width, int ld, const float* packed, float* agg_out, msmp_stream_t stream);
 /* gate_pre == NULL: out = InstanceNorm(main_pre); else out = (1 - tau) h + tau Swish(IN(main_pre)), tau = sigmoid(IN(gate_pre)) */
 int msmp_wide_norm_blend_f32(const float* h, const float* gate_pre, const float* main_pre, const int32_t* graph_ptr, int64_t n_graphs,
                              int width, int ld, float eps, float* out, msmp_stream_t stream);

@@ -95,6 +95,8 @@ class _MPLayerBase(nn.Module):
         self._make_update_net_2(hidden_features, out_features)
         self._packed = None
         self._packed_key = None
+        self._wide_msg = None
+        self._wide_msg_key = None
         self._ps = None
 
     def _params8(self):
@@ -138,6 +140,25 @@ class _MPLayerBase(nn.Module):
             self._packed = (wp, wq) + tuple(p.detach().to(torch.float32).contiguous() for p in ps[1:])
             self._packed_key = key
         return self._packed
+
+    def wide_message_blob(self):
+        """message_net_2 in the layout of the fused wide message kernel (msmp_pack_wide_msg_f32: fp16 hi / lo fragments of W2 2^s, bias 2^s),
+        cached per parameter version like wide_weights(); None where the kernel does not exist (hidden width above 256)."""
+        L = lib()
+        W = self.hidden_features
+        n_floats = L.msmp_packed_wide_msg_floats(W)
+        if n_floats <= 0:
+            return None
+        w2, b2 = self._params8()[2:4]
+        key = (_lib.PARAM_EPOCH[0], w2.data_ptr(), w2._version, b2.data_ptr(), b2._version)
+        if key != self._wide_msg_key:
+            if w2.device.type != 'cuda' or b2.device != w2.device:
+                raise _lib.MsmpError('layer parameters must be on the GPU (HIP path only, no CPU fallback)')
+            blob = torch.empty(n_floats, dtype=torch.float32, device=w2.device)
+            f = [_f32c(w2), _f32c(b2)]
+            check(L.msmp_pack_wide_msg_f32(ptr(f[0]), ptr(f[1]), W, ptr(blob), current_stream()), 'msmp_pack_wide_msg_f32')
+            self._wide_msg, self._wide_msg_key = blob, key
+        return self._wide_msg
 
     def forward(self, x, u, pos, variables, edge_index, batch, structure=None):
         """Same signature as the reference's layer forward (experiments/models_gnn.py:61-67 / 124-130);
@@ -233,13 +254,27 @@ def _wide_head(h, feat_cat, k_feat, variables, gs, layer, ld, ws):
     Q = torch.empty(n, ld, dtype=torch.float32, device=dev)
     _wide_linear(feat_cat, k_feat, wp, b1, W, 0, P, ws)
     _wide_linear(feat_cat, k_feat, wq, None, W, 0, Q, ws)
-    a1 = torch.empty(max(e, 1), ld, dtype=torch.float32, device=dev)
-    check(L.msmp_wide_gather_swish_f32(ptr(P), ptr(Q), ptr(gs.tgt), ptr(gs.col), e, W, ld, ptr(a1), current_stream()), 'msmp_wide_gather_swish_f32')
-    msg = torch.empty(max(e, 1), ld, dtype=torch.float32, device=dev)
-    if e:
-        _wide_linear(a1[:e], W, w2, b2, W, 1, msg[:e], ws)
     agg = torch.empty(n, ld, dtype=torch.float32, device=dev)
-    check(L.msmp_wide_scatter_mean_f32(ptr(msg), ptr(gs.rowptr), n, W, ld, ptr(agg), current_stream()), 'msmp_wide_scatter_mean_f32')
+    fused = False
+    # (msmp_tune("lem_wide", 0) selects the unfused width-generic path as a WHOLE: the model is then independent of "split", bitwise the
+    # exact-fp32 evaluation, which is what that setting is compared against)
+    if L.msmp_tune_query(b'wide_msg') and L.msmp_tune_query(b'split') and L.msmp_tune_query(b'lem_wide'):
+        # the message half as ONE launch, nothing edge-sized in memory (wide_message_kernel.hip); an in-degree above the kernel's cap
+        # (msmp_wide_message_max_in_degree) is refused by value and takes the three launches below, like msmp_edge_aggregate_f32 above 256
+        blob = layer.wide_message_blob()
+        if blob is not None:
+            rc = L.msmp_wide_message_f32(ptr(P), ptr(Q), ptr(gs.rowptr), ptr(gs.col), n, e, gs.max_in_degree, W, ld, ptr(blob), ptr(agg),
+                                         current_stream())
+            if rc != _lib.MSMP_ERR_UNSUPPORTED:
+                check(rc, 'msmp_wide_message_f32')
+                fused = True
+    if not fused:
+        a1 = torch.empty(max(e, 1), ld, dtype=torch.float32, device=dev)
+        check(L.msmp_wide_gather_swish_f32(ptr(P), ptr(Q), ptr(gs.tgt), ptr(gs.col), e, W, ld, ptr(a1), current_stream()), 'msmp_wide_gather_swish_f32')
+        msg = torch.empty(max(e, 1), ld, dtype=torch.float32, device=dev)
+        if e:
+            _wide_linear(a1[:e], W, w2, b2, W, 1, msg[:e], ws)
+        check(L.msmp_wide_scatter_mean_f32(ptr(msg), ptr(gs.rowptr), n, W, ld, ptr(agg), current_stream()), 'msmp_wide_scatter_mean_f32')
     upd_in = torch.cat((h[:, :W], agg[:, :W], variables), 1)
     pad = (-upd_in.shape[1]) % 4
     if pad:

@@ -354,7 +354,11 @@ class _SolverBase(nn.Module):
         dev = dev or next(self.parameters()).device
         for layers in (self.gnn_layers, getattr(self, 'gnn_layers_gate', ())):
             for layer in layers:
-                layer.wide_weights() if layer.wide else layer.packed()
+                if layer.wide:
+                    layer.wide_weights()
+                    layer.wide_message_blob()
+                else:
+                    layer.packed()
         if self.LEM_ENCODER and not self.LSTM_ENCODER and self.hidden_features == 128 and not isinstance(self.embedding_lem, LEMS):
             self.embedding_lem._pack(self.lemoutput_mlp)
         elif not self.LEM_ENCODER and not self.LSTM_ENCODER:
