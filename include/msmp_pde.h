@@ -95,12 +95,16 @@ int msmp_last_status(int* flags_out, int reset);
  *             msmp_wide_message_f32 launch; 0: msmp_wide_gather_swish_f32 + msmp_linear_f32 + msmp_wide_scatter_mean_f32 around two
  *             [E, ld] tensors (the entry itself does not read the key).  The host takes the fused launch only while "split" and
  *             "lem_wide" are 1 as well: "lem_wide" 0 selects the unfused width-generic path as a whole, bitwise the exact-fp32 evaluation.
+ *   "wide_tail" 1: the host's no-grad layer at widths other than 128 evaluates the node half of a layer (both heads of a gated
+ *             pair) as one msmp_wide_node_tail_f32 launch on graphs of up to 128 nodes; 0 (default): per head a concatenation and two
+ *             msmp_linear_f32, then msmp_wide_norm_blend_f32 (the entry itself does not read the key).  The host takes the fused launch only while "wide_msg",
+ *             "split" and "lem_wide" are 1 as well, so each of those keeps selecting the path it selected before this kernel.
  *   "tile_arith" 1 (default): ranged tiles take their node rows by arithmetic on tile_halo; 0: always through the node list.
  *   "tail"    1 (default): msmp_mp_layer_f32 uses msmp_node_tail_f32 for graphs of up to 128 nodes; 0: the piecewise kernels.
  *   "pair"    gated pair: both heads' projection / message kernels in one launch each (bit-identical results): 0 never,
  *             1 (default) for batches of up to 65 536 nodes, where a step is bound by the latency of its ~60 dependent launches, 2 always. */
 int msmp_tune(const char* key, int value);
-int msmp_tune_query(const char* key);      /* current value of "split", "tail", "pair", "bwd_gemm", "tile", "tile_arith", "lem_wide", "wide_msg", ... (0 for unknown keys) */
+int msmp_tune_query(const char* key);      /* current value of "split", "tail", "pair", "bwd_gemm", "tile", "tile_arith", "lem_wide", "wide_msg", "wide_tail", ... (0 for unknown keys) */
 
 /* ---------------------------------------------------------------------------------------------
  * Weights
@@ -556,6 +560,35 @@ int msmp_wide_message_max_in_degree(int width);
  * width outside 1..256, a bad ld, a null or misaligned pointer; n_nodes == 0 is a no-op, n_edges == 0 writes zeros. */
 int msmp_wide_message_f32(const float* p, const float* q, const int32_t* rowptr, const int32_t* col, int64_t n_nodes, int64_t n_edges,
                           int max_in_degree, int width, int ld, const float* packed, float* agg_out, msmp_stream_t stream);
+/* The node half of one layer at any hidden width 1 <= width <= 256 in ONE launch, both heads of a gated pair, on graphs of up to 128 nodes;
+ * neither the concatenated update input nor z nor y goes to memory:
+ *   z_k = Swish(w3_k [h | agg_k | vars] + b3_k)       update_net_1 (experiments/models_gnn.py:140-149)
+ *   y_k = w4_k z_k + b4_k                             update_net_2 (GNN_LayerLin: no activation, no residual)
+ *   n_k = InstanceNorm of y_k per graph and channel, biased variance, eps (:129)
+ *   out = n_main   without a gate head;   out = (1 - tau) h + tau Swish(n_main),  tau = sigmoid(n_gate)   with one (:1486-1489).
+ * One workgroup per graph and fixed-order sums: a graph's rows do not depend on the batch around it or on its position, and two runs
+ * give the same bits.  fp16-split MFMA arithmetic of the default path with node rows scaled by 2^8: an h or agg element with |x| > 255
+ * or not finite raises MSMP_STATUS_NODE_SATURATED, statistics that are not finite raise MSMP_STATUS_NONFINITE.
+ * Blob size / pack (experiments/models_gnn.py:140-149: update_net_1[0].weight [width, 2 width + nv] and .bias, update_net_2[0].weight
+ * [width, width] and .bias, as in the state_dict): scales [8] | b3 [Wp] | b4 [Wp] | the fp16 hi / lo fragments of w3 2^s3 and w4 2^s4,
+ * zero-filled up to Wp = 32 KT, KT = ceil(width / 32): 8 + 576 KT + 3072 KT^2 floats whatever nv is (the variables take one K = 16 step);
+ * the powers of two are chosen on the device.  0 and msmp_last_error for a width outside 1..256 or nv outside 0..8. */
+int64_t msmp_packed_wide_tail_floats(int width, int nv);
+int msmp_pack_wide_tail_f32(const float* w3, const float* b3, const float* w4, const float* b4, int width, int nv, float* packed_out,
+                            msmp_stream_t stream);
+/* experiments/models_gnn.py:129: the largest graph (nodes) msmp_wide_node_tail_f32 takes at this width: 128, the InstanceNorm statistics
+ * of a graph stay in one workgroup's registers; 0 and msmp_last_error for a width outside 1..256. */
+int msmp_wide_node_tail_max_graph_nodes(int width);
+/* experiments/models_gnn.py:140-149, :129, :1486-1489.  h, agg_main, agg_gate, out [n_nodes, ld] with ld a multiple of 4 in width .. 4096,
+ * 16-byte aligned (columns width .. ld - 1 of the inputs are not used, of out they are written as 0; nothing outside out is written);
+ * vars [n_nodes, nv], nv 0..8; graph_ptr [n_graphs + 1] node offsets; max_graph_nodes: an upper bound of the graph sizes
+ * (GraphStructure.max_graph_nodes).  agg_gate == packed_gate == NULL selects the form without a gate head; one without the other is
+ * MSMP_ERR_ARG.  MSMP_ERR_UNSUPPORTED for max_graph_nodes above msmp_wide_node_tail_max_graph_nodes(width) or a width outside 1..256 (the
+ * caller keeps the row GEMMs and msmp_wide_norm_blend_f32, as with msmp_node_tail_f32 above 128 nodes); MSMP_ERR_ARG for a null or
+ * misaligned pointer, a bad ld, nv outside 0..8 or negative sizes; n_nodes == 0 is a no-op.  Allocates nothing and never synchronises. */
+int msmp_wide_node_tail_f32(const float* h, const float* agg_main, const float* agg_gate, const float* vars, const int32_t* graph_ptr,
+                            int64_t n_nodes, int64_t n_graphs, int max_graph_nodes, int nv, int width, int ld, const float* packed_main,
+                            const float* packed_gate, float eps, float* out, msmp_stream_t stream);
 /* gate_pre == NULL: out = InstanceNorm(main_pre); else out = (1 - tau) h + tau Swish(IN(main_pre)), tau = sigmoid(IN(gate_pre)) */
 int msmp_wide_norm_blend_f32(const float* h, const float* gate_pre, const float* main_pre, const int32_t* graph_ptr, int64_t n_graphs,
                              int width, int ld, float eps, float* out, msmp_stream_t stream);

@@ -1427,6 +1427,7 @@ extern int g_lem_tail;
 extern int g_lem_share;
 extern int g_lem_wide;
 extern int g_wide_msg;
+extern int g_wide_tail;
 // the sticky range status is the fp16-split path's: the exact-fp32 kernels have no range to leave (they run the data the split path could not)
 static int* split_status() { return msmp_tune_get("split") ? msmp::status_ptr() : nullptr; }
 static int g_split = 1;      // fp16-split matrix path (default); msmp_tune("split", 0) selects the fp32-MFMA kernels
@@ -1493,6 +1494,7 @@ int msmp_tune_get(const char* key) {
     if (!strcmp(key, "lem_share")) return g_lem_share;
     if (!strcmp(key, "lem_wide")) return g_lem_wide;
     if (!strcmp(key, "wide_msg")) return g_wide_msg;
+    if (!strcmp(key, "wide_tail")) return g_wide_tail;
     return 0;
 }
 
@@ -1511,6 +1513,7 @@ extern "C" int msmp_tune(const char* key, int value) {
     if (key && !strcmp(key, "lem_share") && value >= 1 && value <= 16) { g_lem_share = value; return MSMP_OK; }
     if (key && !strcmp(key, "lem_wide")) { g_lem_wide = value != 0; return MSMP_OK; }
     if (key && !strcmp(key, "wide_msg")) { g_wide_msg = value != 0; return MSMP_OK; }
+    if (key && !strcmp(key, "wide_tail")) { g_wide_tail = value != 0; return MSMP_OK; }
     if (key && !strcmp(key, "edge_nb")) { g_edge_nb = value; return MSMP_OK; }
     if (key && !strcmp(key, "split")) { g_split = value; return MSMP_OK; }
     msmp::set_error("msmp_tune: unknown key");

@@ -97,6 +97,8 @@ class _MPLayerBase(nn.Module):
         self._packed_key = None
         self._wide_msg = None
         self._wide_msg_key = None
+        self._wide_tail = None
+        self._wide_tail_key = None
         self._ps = None
 
     def _params8(self):
@@ -159,6 +161,27 @@ class _MPLayerBase(nn.Module):
             check(L.msmp_pack_wide_msg_f32(ptr(f[0]), ptr(f[1]), W, ptr(blob), current_stream()), 'msmp_pack_wide_msg_f32')
             self._wide_msg, self._wide_msg_key = blob, key
         return self._wide_msg
+
+    def wide_tail_blob(self):
+        """update_net_1 / update_net_2 in the layout of the fused wide node tail (msmp_pack_wide_tail_f32: fp16 hi / lo fragments of W3 2^s3 and
+        W4 2^s4, scaled biases), cached per parameter version like wide_message_blob(); None where the kernel does not exist (hidden width
+        above 256)."""
+        L = lib()
+        W, nv = self.hidden_features, self.n_variables
+        n_floats = L.msmp_packed_wide_tail_floats(W, nv)
+        if n_floats <= 0:
+            return None
+        ps = self._params8()[4:8]
+        key = (_lib.PARAM_EPOCH[0],) + tuple((p.data_ptr(), p._version) for p in ps)
+        if key != self._wide_tail_key:
+            if ps[0].device.type != 'cuda' or any(p.device != ps[0].device for p in ps):
+                raise _lib.MsmpError('layer parameters must be on the GPU (HIP path only, no CPU fallback)')
+            blob = torch.empty(n_floats, dtype=torch.float32, device=ps[0].device)
+            f = [_f32c(p) for p in ps]
+            check(L.msmp_pack_wide_tail_f32(ptr(f[0]), ptr(f[1]), ptr(f[2]), ptr(f[3]), W, nv, ptr(blob), current_stream()),
+                  'msmp_pack_wide_tail_f32')
+            self._wide_tail, self._wide_tail_key = blob, key
+        return self._wide_tail
 
     def forward(self, x, u, pos, variables, edge_index, batch, structure=None):
         """Same signature as the reference's layer forward (experiments/models_gnn.py:61-67 / 124-130);
@@ -244,8 +267,8 @@ def _wide_linear(x, k, w, bias, n_out, mode, out, ws):
                             ptr(ws), ws.numel(), current_stream()), 'msmp_linear_f32')
 
 
-def _wide_head(h, feat_cat, k_feat, variables, gs, layer, ld, ws):
-    """One GNN_LayerLin head at hidden width W != 128 up to its pre-norm output [N, ld] (experiments/models_gnn.py:124-149)."""
+def _wide_head_aggregate(h, feat_cat, k_feat, gs, layer, ld, ws):
+    """The message half of one GNN_LayerLin head at hidden width W != 128: the mean aggregate [N, ld] (experiments/models_gnn.py:132-138, :107)."""
     L = lib()
     n, W, e = h.shape[0], layer.hidden_features, gs.n_edges
     wp, wq, b1, w2, b2, w3, b3, w4, b4 = layer.wide_weights()
@@ -275,6 +298,13 @@ def _wide_head(h, feat_cat, k_feat, variables, gs, layer, ld, ws):
         if e:
             _wide_linear(a1[:e], W, w2, b2, W, 1, msg[:e], ws)
         check(L.msmp_wide_scatter_mean_f32(ptr(msg), ptr(gs.rowptr), n, W, ld, ptr(agg), current_stream()), 'msmp_wide_scatter_mean_f32')
+    return agg
+
+
+def _wide_head_update(h, agg, variables, layer, ld, ws):
+    """The update half of one head as two row GEMMs, up to its pre-norm output [N, ld] (experiments/models_gnn.py:140-149)."""
+    n, W, dev = h.shape[0], layer.hidden_features, h.device
+    w3, b3, w4, b4 = layer.wide_weights()[5:9]
     upd_in = torch.cat((h[:, :W], agg[:, :W], variables), 1)
     pad = (-upd_in.shape[1]) % 4
     if pad:
@@ -305,11 +335,25 @@ def _mp_layer_wide(h, u, pos_x, variables, gs, main, gate, eps):
     feat_cat = feat_cat.contiguous()
     k_max = max(feat_cat.shape[1], 2 * W + variables.shape[1] + 3)
     ws = _Workspace.get(L.msmp_linear_workspace_bytes(k_max, W), h.device)
-    y_main = _wide_head(hp, feat_cat, k_feat, variables, gs, main, ld, ws)
-    y_gate = _wide_head(hp, feat_cat, k_feat, variables, gs, gate, ld, ws) if gate is not None else None
+    heads = [main] if gate is None else [main, gate]
+    aggs = [_wide_head_aggregate(hp, feat_cat, k_feat, gs, layer, ld, ws) for layer in heads]
     out = torch.empty(n, ld, dtype=torch.float32, device=h.device)
-    check(L.msmp_wide_norm_blend_f32(ptr(hp), ptr(y_gate), ptr(y_main), ptr(gs.graph_ptr), gs.n_graphs, W, ld, eps, ptr(out), current_stream()),
-          'msmp_wide_norm_blend_f32')
+    # the node half of the layer as ONE launch (wide_node_tail_kernel.hip) while every switch of the fused width-generic path is on: each
+    # of "wide_msg", "split" and "lem_wide" at 0 keeps selecting exactly the path it selected before that kernel existed.  A graph above
+    # the kernel's cap (msmp_wide_node_tail_max_graph_nodes) is refused by value and takes the GEMMs below, like msmp_node_tail_f32 above 128
+    if (all(L.msmp_tune_query(k) for k in (b'wide_tail', b'wide_msg', b'split', b'lem_wide'))
+            and gs.max_graph_nodes <= L.msmp_wide_node_tail_max_graph_nodes(min(W, 256))):
+        blobs = [layer.wide_tail_blob() for layer in heads]
+        if all(b is not None for b in blobs):
+            rc = L.msmp_wide_node_tail_f32(ptr(hp), ptr(aggs[0]), ptr(aggs[1]) if gate is not None else None, ptr(variables), ptr(gs.graph_ptr), n,
+                                           gs.n_graphs, gs.max_graph_nodes, variables.shape[1], W, ld, ptr(blobs[0]),
+                                           ptr(blobs[1]) if gate is not None else None, eps, ptr(out), current_stream())
+            if rc != _lib.MSMP_ERR_UNSUPPORTED:
+                check(rc, 'msmp_wide_node_tail_f32')
+                return out[:, :W].contiguous()
+    ys = [_wide_head_update(hp, agg, variables, layer, ld, ws) for layer, agg in zip(heads, aggs)]
+    check(L.msmp_wide_norm_blend_f32(ptr(hp), ptr(ys[1]) if gate is not None else None, ptr(ys[0]), ptr(gs.graph_ptr), gs.n_graphs, W, ld, eps, ptr(out),
+                                     current_stream()), 'msmp_wide_norm_blend_f32')
     return out[:, :W].contiguous()
 
 

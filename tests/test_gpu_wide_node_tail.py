@@ -1,0 +1,320 @@
+"""GPU tests of the fused width-generic node tail (msmp_wide_node_tail_f32, wide_node_tail_kernel.hip): update_net_1, update_net_2, InstanceNorm
+and the gated blend of GNN_LayerLin (experiments/models_gnn.py:140-149, :129, :1486-1489) in one launch at any hidden width up to 256 on
+graphs of up to 128 nodes, against the formula in numpy float64 (O.node_update / O.instance_norm) from the same fp32 inputs; its bitwise
+properties (run to run, independent of the batch around a graph), the padding columns, the graph-size cap and the fall-back above it, the
+range status, and the host paths that reach it: layers._mp_layer_wide and the two GLU solver classes.
+Bar: 5e-6 max(1, (2 W + nv) / 258) where every graph of more than one node has at least 30 nodes (5e-6 is the bar of test_node_tail_vs_oracle
+for this arithmetic at the 128-wide tail's K = 258; the rounding sum grows at most linearly in K), 2e-4 otherwise (InstanceNorm over a
+2-5 node graph amplifies fp32 rounding: that test's rule)."""
+import numpy as np
+import pytest
+import torch
+
+from oracle import msmp_oracle as O
+from helpers import synthetic_case
+
+pytestmark = pytest.mark.gpu
+
+WIDTHS = [33, 96, 128, 130, 164, 192, 256]          # KT 2, 3, 4, 5, 6, 6, 8
+BATCHES = [(2, [100, 100, 37, 1, 64]), (3, [128, 5, 90, 127]), (1, [2, 3, 33])]      # the batches of test_node_tail_vs_oracle
+EPS = 1e-5
+
+
+@pytest.fixture(scope='module')
+def mp():
+    import msmp_pde_amd
+    assert torch.cuda.is_available()
+    msmp_pde_amd.lib()
+    return msmp_pde_amd
+
+
+@pytest.fixture(autouse=True)
+def _restore_switches(mp):
+    yield
+    for key in (b'wide_tail', b'wide_msg', b'split', b'lem_wide'):
+        mp.lib().msmp_tune(key, 1)
+    mp.lib().msmp_tune(b'wide_tail', DEFAULT_WIDE_TAIL[0])
+
+
+DEFAULT_WIDE_TAIL = [None]
+
+
+@pytest.fixture(scope='module', autouse=True)
+def _default(mp):
+    DEFAULT_WIDE_TAIL[0] = mp.lib().msmp_tune_query(b'wide_tail')
+
+
+def ld_of(W):
+    return 128 * ((W + 127) // 128)
+
+
+class Case(object):
+    """update_net_1 / update_net_2 of two GNN_LayerLin heads at width W (the reference's initialisation) and their packed blobs; h and
+    both aggregates standard normal with row stride ld, variables uniform in [0, 1)"""
+
+    def __init__(self, mp, W, nv, sizes, ld, seed=0):
+        from msmp_pde_amd._lib import ptr, current_stream
+        torch.manual_seed(1000 * W + 10 * nv + seed)
+        self.W, self.nv, self.ld, self.sizes, self.n = W, nv, ld, list(sizes), int(sum(sizes))
+        self.batch = np.repeat(np.arange(len(sizes)), sizes)
+        self.gptr = torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int32, device='cuda')
+        L = mp.lib()
+        self.params, self.blobs = [], []
+        for _ in range(2):
+            layer = mp.GNN_LayerLin(W, W, W, 25, nv).cuda()
+            sd = {k: v.detach() for k, v in layer.state_dict().items()}
+            self.params.append(O.layer_params({k: v.double().cpu().numpy() for k, v in sd.items()}, ''))
+            nf = L.msmp_packed_wide_tail_floats(W, nv)
+            assert nf > 0
+            blob = torch.empty(nf, dtype=torch.float32, device='cuda')
+            w = [sd[k].contiguous() for k in ('update_net_1.0.weight', 'update_net_1.0.bias', 'update_net_2.0.weight', 'update_net_2.0.bias')]
+            assert w[0].shape == (W, 2 * W + nv) and w[2].shape == (W, W)
+            assert L.msmp_pack_wide_tail_f32(ptr(w[0]), ptr(w[1]), ptr(w[2]), ptr(w[3]), W, nv, ptr(blob), current_stream()) == 0
+            self.blobs.append(blob)
+        torch.cuda.synchronize()
+        n = self.n
+        self.h = torch.randn(n, ld, device='cuda')
+        self.agg = [torch.randn(n, ld, device='cuda') for _ in range(2)]
+        self.var = torch.rand(n, nv, device='cuda')
+        self._ref = {}
+
+    def reference(self, gated):
+        """float64 from the fp32 inputs, computed once per form: [n, W]"""
+        if gated not in self._ref:
+            W = self.W
+            h64, var64 = self.h.double().cpu().numpy()[:, :W], self.var.double().cpu().numpy()
+            pre = lambda k: O.instance_norm(O.node_update(self.params[k], h64, self.agg[k].double().cpu().numpy()[:, :W], var64, True), self.batch, EPS)
+            if gated:
+                tau = O.sigmoid(pre(1))
+                self._ref[gated] = (1.0 - tau) * h64 + tau * O.swish(pre(0))
+            else:
+                self._ref[gated] = pre(0)
+        return self._ref[gated]
+
+    def bar(self):
+        big = min(s for s in self.sizes if s > 1) >= 30
+        return 5e-6 * max(1.0, (2 * self.W + self.nv) / 258.0) if big else 2e-4
+
+
+def run(mp, case, gated, out=None, n_graphs=None, max_nodes=None):
+    from msmp_pde_amd._lib import ptr, current_stream
+    n_graphs = len(case.sizes) if n_graphs is None else n_graphs
+    n = int(sum(case.sizes[:n_graphs]))
+    if out is None:
+        out = torch.full((n, case.ld), float('nan'), device='cuda')
+    rc = mp.lib().msmp_wide_node_tail_f32(ptr(case.h), ptr(case.agg[0]), ptr(case.agg[1]) if gated else None, ptr(case.var), ptr(case.gptr), n, n_graphs,
+                                          max(case.sizes) if max_nodes is None else max_nodes, case.nv, case.W, case.ld, ptr(case.blobs[0]),
+                                          ptr(case.blobs[1]) if gated else None, EPS, out.data_ptr(), current_stream())
+    torch.cuda.synchronize()
+    return rc, out
+
+
+def check(case, out, gated, what):
+    W = case.W
+    got, ref = out.double().cpu().numpy(), case.reference(gated)
+    e, bar = float(np.abs(got[:, :W] - ref).max()), case.bar()
+    print(f'{what} ({"gated" if gated else "plain"}): max abs err {e:.2e} (bar {bar:.2e})')
+    assert e < bar, (what, gated, e, bar)
+    assert (got[:, W:] == 0).all(), what
+
+
+@pytest.mark.parametrize('nv,sizes', BATCHES)
+@pytest.mark.parametrize('W,extra', [(w, 0) for w in WIDTHS] + [(164, 8)])
+def test_parity(mp, W, extra, nv, sizes):
+    case = Case(mp, W, nv, sizes, ld_of(W) + extra)
+    for gated in (True, False):
+        rc, out = run(mp, case, gated)
+        assert rc == 0
+        check(case, out, gated, f'W={W} ld={case.ld} nv={nv} sizes={sizes}')
+        if not gated:
+            for g, s in enumerate(sizes):
+                if s == 1:                                    # a 1-node graph: y - mean is an exact 0
+                    row = int(sum(sizes[:g]))
+                    assert (out[row] == 0).all()
+    assert mp.last_status() == 0
+
+
+def test_more_graphs_than_resident_workgroups(mp):
+    """600 graphs of 10 nodes at width 164: more than a persistent launch has workgroups (one per CU), so every workgroup loops"""
+    case = Case(mp, 164, 2, [10] * 600, 256, seed=1)
+    for gated in (True, False):
+        rc, out = run(mp, case, gated)
+        assert rc == 0
+        check(case, out, gated, '600 graphs of 10 nodes')
+
+
+@pytest.mark.parametrize('W', [33, 164, 256])
+def test_runs_repeat_and_graphs_do_not_depend_on_the_batch(mp, W):
+    case = Case(mp, W, 2, [100, 100, 37, 1, 64], ld_of(W), seed=2)
+    for gated in (True, False):
+        rc1, a = run(mp, case, gated)
+        rc2, b = run(mp, case, gated)
+        assert rc1 == 0 and rc2 == 0 and torch.equal(a, b)
+        rc, sub = run(mp, case, gated, n_graphs=2)              # the first two graphs alone: other workgroups, another grid
+        assert rc == 0 and torch.equal(sub, a[:200])
+
+
+def test_padding_columns_are_zero_and_nothing_else_is_written(mp):
+    W, ld = 164, 256 + 8
+    case = Case(mp, W, 2, [100, 100, 37, 1, 64], ld, seed=3)
+    n = case.n
+    poison, pad = 777.25, 4096
+    for gated in (True, False):
+        buf = torch.full((pad + n * ld + pad,), poison, device='cuda')
+        out = buf[pad:pad + n * ld].view(n, ld)
+        rc, _ = run(mp, case, gated, out=out)
+        assert rc == 0
+        assert (buf[:pad] == poison).all() and (buf[pad + n * ld:] == poison).all()
+        assert (out[:, W:] == 0).all() and not (out[:, :W] == poison).any()
+        check(case, out, gated, 'poisoned buffer')
+
+
+def ragged_edges(sizes, seed=3):
+    """the graphs of test_wide_layer_pieces_vs_oracle: every seventh target without in-edges, in-degrees 1-5"""
+    rng = np.random.default_rng(seed)
+    starts = np.concatenate(([0], np.cumsum(sizes)))
+    src, dst = [], []
+    for g, sz in enumerate(sizes):
+        for t in range(sz):
+            if t % 7 == 3:
+                continue
+            for s_ in rng.choice(sz, size=min(sz, int(rng.integers(1, 6))), replace=False):
+                src.append(starts[g] + s_); dst.append(starts[g] + t)
+    order = np.argsort(np.array(dst), kind='stable')
+    ei = np.stack([np.array(src)[order], np.array(dst)[order]])
+    return ei, np.repeat(np.arange(len(sizes)), sizes), int(sum(sizes))
+
+
+def layer_inputs(n, W, tw, nv, seed):
+    rng = np.random.default_rng(seed)
+    h = torch.tensor(rng.standard_normal((n, W)), dtype=torch.float32).cuda()
+    u = torch.tensor(rng.standard_normal((n, tw)), dtype=torch.float32).cuda()
+    pos = torch.tensor(rng.uniform(0, 1, (n, 1)), dtype=torch.float32).cuda()
+    var = torch.tensor(rng.uniform(0, 1, (n, nv)), dtype=torch.float32).cuda()
+    return h, u, pos, var
+
+
+def oracle_layer(main, gate, args, ei, batch):
+    args64 = [t.double().cpu().numpy() for t in args]
+    sd = lambda m: {k: v.detach().double().cpu().numpy() for k, v in m.state_dict().items()}
+    ref = O.mp_layer(O.layer_params(sd(main), ''), *args64, ei, batch, lin=True)
+    if gate is None:
+        return ref
+    tau = O.sigmoid(O.mp_layer(O.layer_params(sd(gate), ''), *args64, ei, batch, lin=True))
+    return (1.0 - tau) * args64[0] + tau * O.swish(ref)
+
+
+def counted_entry(mp, monkeypatch):
+    L = mp.lib()
+    real, calls = L.msmp_wide_node_tail_f32, []
+
+    def counted(*a):
+        calls.append(1)
+        return real(*a)
+    monkeypatch.setattr(L, 'msmp_wide_node_tail_f32', counted)
+    return calls
+
+
+def test_a_graph_above_the_cap_is_refused_and_the_layer_takes_the_gemms(mp, monkeypatch):
+    from msmp_pde_amd.layers import _mp_layer_wide
+    from msmp_pde_amd.graph import GraphStructure
+    W, tw, nv = 164, 25, 2
+    L = mp.lib()
+    assert L.msmp_wide_node_tail_max_graph_nodes(W) == 128
+    case = Case(mp, W, nv, [100, 100, 37, 1, 64], 256, seed=4)
+    out = torch.full((case.n, 256), 7.5, device='cuda')
+    rc, out = run(mp, case, True, out=out, max_nodes=129)
+    assert rc == -2 and b'max_graph_nodes' in L.msmp_last_error()
+    assert (out == 7.5).all()                                 # nothing was launched
+    sizes = [1, 37, 100, 130, 5]
+    ei, batch, n = ragged_edges(sizes)
+    gs = GraphStructure(torch.tensor(ei).cuda(), torch.tensor(batch).cuda(), n)
+    assert gs.max_graph_nodes == 130
+    torch.manual_seed(9)
+    main, gate = mp.GNN_LayerLin(W, W, W, tw, nv).cuda(), mp.GNN_LayerLin(W, W, W, tw, nv).cuda()
+    h, u, pos, var = layer_inputs(n, W, tw, nv, 4)
+    L.msmp_tune(b'wide_tail', 1)
+    calls = counted_entry(mp, monkeypatch)
+    with torch.no_grad():
+        got = _mp_layer_wide(h, u, pos.reshape(-1), var, gs, main, gate, EPS)
+    assert not calls                                          # the host asks msmp_wide_node_tail_max_graph_nodes first
+    e = np.abs(got.double().cpu().numpy() - oracle_layer(main, gate, (h, u, pos, var), ei, batch)).max()
+    print(f'layer with a 130-node graph: {e:.2e}')
+    assert e < 2e-5
+
+
+def test_out_of_range_row_raises_the_status(mp):
+    case = Case(mp, 164, 2, [100, 100, 37, 1, 64], 256, seed=5)
+    mp.last_status(reset=True)
+    rc, _ = run(mp, case, True)
+    assert rc == 0 and mp.last_status() == 0
+    case.h *= 5000.0
+    rc, _ = run(mp, case, True)
+    assert rc == 0
+    assert mp.last_status(reset=True) & mp.MSMP_STATUS_NODE_SATURATED
+    assert mp.last_status() == 0
+
+
+@pytest.mark.parametrize('gated', [False, True])
+def test_layer_takes_one_fused_tail_call(mp, gated, monkeypatch):
+    from msmp_pde_amd.layers import _mp_layer_wide
+    from msmp_pde_amd.graph import GraphStructure
+    from msmp_pde_amd import _lib
+    W, tw, nv = 164, 25, 2
+    ei, batch, n = ragged_edges([1, 37, 100, 128, 5])
+    gs = GraphStructure(torch.tensor(ei).cuda(), torch.tensor(batch).cuda(), n)
+    assert gs.max_graph_nodes == 128
+    torch.manual_seed(5)
+    main = mp.GNN_LayerLin(W, W, W, tw, nv).cuda()
+    gate = mp.GNN_LayerLin(W, W, W, tw, nv).cuda() if gated else None
+    h, u, pos, var = layer_inputs(n, W, tw, nv, 3)
+    ref = oracle_layer(main, gate, (h, u, pos, var), ei, batch)
+    L = mp.lib()
+    calls = counted_entry(mp, monkeypatch)
+    layer = lambda: _mp_layer_wide(h, u, pos.reshape(-1), var, gs, main, gate, EPS)
+    with torch.no_grad():
+        L.msmp_tune(b'wide_tail', 1)
+        out1 = layer()
+        assert len(calls) == 1                                # one launch for the layer, both heads
+        e = np.abs(out1.double().cpu().numpy() - ref).max()
+        print(f'wide layer ({"gated" if gated else "plain"}) with wide_tail 1: {e:.2e}')
+        assert e < 2e-5
+        del calls[:]
+        L.msmp_tune(b'wide_tail', 0)
+        out0 = layer()                                        # concatenation + row GEMMs + norm / blend: the path before this kernel
+        with _lib.exact_fp32():
+            exact0 = layer()
+        L.msmp_tune(b'wide_msg', 0)
+        before = layer()                                      # ... and the path before the fused message kernel
+        L.msmp_tune(b'wide_msg', 1)
+        L.msmp_tune(b'wide_tail', 1)
+        with _lib.exact_fp32():
+            exact1 = layer()
+        assert not calls                                      # none of the four reaches the fused entry
+    assert np.abs(out0.double().cpu().numpy() - ref).max() < 2e-5
+    # the exact-fp32 evaluation does not depend on the switch, and it is the unfused path bit for bit.  (`out0` itself still takes the
+    # fused fp16-split MESSAGE kernel, as it did before this switch existed, so it equals neither: it is held to the oracle above.)
+    assert torch.equal(exact1, exact0) and torch.equal(exact0, before)
+
+
+@pytest.mark.parametrize('kind,exp', [('MP_PDE_SolverLEMLinGatedGLU', 'E2'), ('MP_PDE_Solver2DLEMLinGatedGLU', 'MSWG3')])
+def test_glu_solver_forward_on_either_tail_path(mp, kind, exp, monkeypatch):
+    torch.manual_seed(7)
+    case = synthetic_case(mp, exp, bsz=2, seed=3)
+    model = getattr(mp, kind)(case.pde, time_window=25, eq_variables=case.eqv, hidden_layer=2).cuda().eval()
+    graph = case.graph.to('cuda')
+    L = mp.lib()
+    calls = counted_entry(mp, monkeypatch)
+    with torch.no_grad():
+        L.msmp_tune(b'wide_tail', 1)
+        out1 = model(graph)
+        assert len(calls) == 2                                # hidden_layer = 2 gated pairs, one launch each
+        L.msmp_tune(b'wide_tail', 0)
+        out0 = model(graph)
+        assert len(calls) == 2
+        L.msmp_tune(b'wide_tail', 1)
+        d = (out1 - out0).abs().max().item()
+        print(f'{kind}/{exp}: wide_tail 1 vs 0 max abs {d:.2e} (output max {out0.abs().max().item():.2e})')
+        assert torch.isfinite(out1).all() and d < 1e-5
+        step = model.capture(graph)                           # the entry allocates nothing and never synchronises: it can be captured
+        assert torch.equal(step(graph), out1)
