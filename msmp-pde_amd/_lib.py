@@ -186,6 +186,29 @@ def _install_optimizer_hook():
 
 _install_optimizer_hook()
 
+
+class PackedCache:
+    """One cached operand derived from parameters (a packed weight blob): rebuilt when PARAM_EPOCH, or the address, version, device
+    or dtype of one of the parameters changed.  `value` is the operand of the last build (None before the first)."""
+    __slots__ = ('key', 'value')
+
+    def __init__(self):
+        self.key = self.value = None
+
+    def get(self, params, build):
+        key = (PARAM_EPOCH[0],) + tuple((p.data_ptr(), p._version, p.device, p.dtype) for p in params)
+        if key != self.key:
+            dev = params[0].device
+            if dev.type != 'cuda' or any(p.device != dev for p in params):
+                raise MsmpError('layer parameters must be on the GPU (HIP path only, no CPU fallback)')
+            self.value, self.key = build(), key
+        return self.value
+
+
+def cached_operands(model):
+    """Every operand the PackedCaches of `model`'s modules hold right now: what a captured graph that read them has to keep alive."""
+    return [c.value for m in model.modules() for c in vars(m).values() if isinstance(c, PackedCache) and c.value is not None]
+
 _raw_stream = None
 
 

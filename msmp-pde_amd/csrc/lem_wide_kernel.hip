@@ -10,8 +10,7 @@
 //   * an A fragment (gate g, slice T, k-step) has exactly ONE consumer wave in the workgroup, so it goes from L2 straight into that
 //     wave's registers through a three-slot ring (two k-steps ahead), and is used for both node tiles; the LDS has no room for a second
 //     copy of the weights beside the states, and staging them there would add a write and a read per fragment for no reuse.
-// Arithmetic as everywhere on the default path (mfma_tiles.h): fp16 2-way split of both operands, three v_mfma_f32_32x32x16_f16 per K = 16
-// step into one fp32 accumulator, weights pre-multiplied by a power of two chosen at pack time; bias + W[:, W:] x_t enter as one or two
+// Fragments and the three-MFMA step are those of wide_frags.h; bias + W[:, W:] x_t enter as one or two
 // K = 16 "slot" MFMAs on a zero accumulator (lem_slot_feature, lem_layout.h), and s(a) tanh(b) is evaluated with one reciprocal as in
 // lem_encoder_ws3_kernel.  Channels W .. Wp - 1 carry zero weights, zero bias and zero state (their update keeps an exact 0) and are
 // never written.  A node's arithmetic depends on nothing but its own row: not on the step index, the workgroup or the tile slot.
@@ -19,10 +18,10 @@
 //             phase 2  g1 (B = y), lin (B = z)                               | barrier (every wave has read y)
 //                      y update, publish y                                   | barrier
 #include "lem_layout.h"
+#include "wide_frags.h"
 
 namespace msmp {
 
-constexpr int LEMW_MAX_W = 256;
 constexpr int LEMW_NT = 2;          // node tiles per workgroup (registers and LDS allow no third at Wp = 256)
 
 // packed blob (floats): scales [8] (2^s of W, Wz, 0, 0, then 2^-s) |
@@ -48,29 +47,9 @@ struct LemWidePackArgs {
 
 // scales[i] = 2^s with max(|M_i|, |b_i|) 2^s in [16, 32) for (W, b), (Wz, bz); scales[4 + i] = 2^-s.  grid = 2.
 __global__ __launch_bounds__(256) void pack_lem_wide_scale_kernel(LemWidePackArgs a) {
-    __shared__ float red[256];
     const int kin = a.width + a.ninp, rows = blockIdx.x == 0 ? 3 * a.width : a.width;
-    const float* w = blockIdx.x == 0 ? a.w : a.wz;
-    const float* b = blockIdx.x == 0 ? a.b : a.bz;
-    float m = 0.f;
-    for (int i = threadIdx.x; i < rows * kin; i += 256) m = fmaxf(m, fabsf(w[i]));
-    for (int i = threadIdx.x; i < rows; i += 256) m = fmaxf(m, fabsf(b[i]));
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + off]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const float mx = red[0];
-        int e = 0;
-        if (mx > 0.f && mx < 3.0e38f) (void)frexpf(mx, &e);
-        const int sft = mx > 0.f ? 5 - e : 0;
-        a.out[blockIdx.x] = ldexpf(1.0f, sft);
-        a.out[4 + blockIdx.x] = ldexpf(1.0f, -sft);
-        a.out[2 + blockIdx.x] = 0.f;
-        a.out[6 + blockIdx.x] = 0.f;
-    }
+    const int sft = block_scale_shift(fmaxf(abs_max_part(blockIdx.x == 0 ? a.w : a.wz, rows * kin), abs_max_part(blockIdx.x == 0 ? a.b : a.bz, rows)));
+    if (threadIdx.x == 0) store_scale_group(a.out, blockIdx.x, sft, 0);
 }
 
 // row `row` (< width) of gate g in consumption order: g2, g3, g1 are rows W.., 2W.., 0.. of `weights`, lin is weights_lin_z
@@ -88,16 +67,11 @@ __global__ void pack_lem_wide_kernel(LemWidePackArgs a) {
     const float* sc = a.out + L.scales;
     const int kt = a.kt, W = a.width, P = a.ninp;
     const int64_t tid0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
-    _Float16* rec = reinterpret_cast<_Float16*>(a.out + L.rec);
-    const int64_t n_rec = (int64_t)8192 * kt * kt;
-    for (int64_t p = tid0; p < n_rec; p += stride) {
-        const int j = (int)(p & 7), lane = (int)(p >> 3) & 63, plane = (int)(p >> 9) & 1;
-        const int fr = (int)(p >> 10), ks = fr % (2 * kt), T = (fr / (2 * kt)) % kt, g = fr / (2 * kt * kt);
+    pack_split_fragments(reinterpret_cast<_Float16*>(a.out + L.rec), (int64_t)8 * kt * kt, [&](int fr, int lane, int j) {
+        const int ks = fr % (2 * kt), T = (fr / (2 * kt)) % kt, g = fr / (2 * kt * kt);
         const int row = 32 * T + (lane & 31), k = 32 * (ks >> 1) + split_k_acc(ks & 1, lane >> 5, j);
-        const float w = row < W && k < W ? lemw_weight(a, g, row, k) * sc[g < 3 ? 0 : 1] : 0.f;
-        const _Float16 hi = (_Float16)w;
-        rec[p] = plane == 0 ? hi : (_Float16)(w - (float)hi);
-    }
+        return row < W && k < W ? lemw_weight(a, g, row, k) * sc[g < 3 ? 0 : 1] : 0.f;
+    });
     _Float16* wh = reinterpret_cast<_Float16*>(a.out + L.wxh);
     const int64_t n_wx = (int64_t)4096 * kt;
     for (int64_t p = tid0; p < n_wx; p += stride) {
@@ -134,30 +108,19 @@ struct LemWideArgs {
     int* status;
 };
 
-// the A fragments of two gates in flight: slot ks % 3 holds k-step ks
+// the A fragments of two gates in flight (two k-steps ahead of their MFMAs): slot ks % 3 holds k-step ks
 struct LemWideRing {
     half8 h0[3], l0[3], h1[3], l1[3];
 };
-
-// Every fragment address is  a wave-uniform base  +  ONE opaque per-lane byte offset (lane * 16, kept in a register the compiler cannot
-// see through)  +  a compile-time constant: left to itself the compiler keeps the ~100 distinct fragment addresses of the unrolled step
-// as loop invariants in vector registers and spills them (the finding behind lem_ws3_gemm2 of lem_kernel.hip).
-__device__ __forceinline__ half8 lemw_gfrag(const half8* base, int frag, unsigned lo) {
-    return *reinterpret_cast<const half8*>(reinterpret_cast<const char*>(base + frag * 64) + lo);
-}
-__device__ __forceinline__ half8 lemw_lfrag(const char* lane_base, int frag) {
-    return *reinterpret_cast<const half8*>(lane_base + frag * 1024);
-}
-
-__device__ __forceinline__ void lemw_ring_load(LemWideRing& r, const half8* w0, const half8* w1, unsigned lo, int ks_slot, int ks) {
-    r.h0[ks_slot] = lemw_gfrag(w0, ks * 2 + 0, lo);
-    r.l0[ks_slot] = lemw_gfrag(w0, ks * 2 + 1, lo);
-    r.h1[ks_slot] = lemw_gfrag(w1, ks * 2 + 0, lo);
-    r.l1[ks_slot] = lemw_gfrag(w1, ks * 2 + 1, lo);
+__device__ __forceinline__ void lemw_ring_load(LemWideRing& r, const half8* w0, const half8* w1, unsigned lo, int ks) {
+    r.h0[ks % 3] = frag_global(w0, ks * 2 + 0, lo);
+    r.l0[ks % 3] = frag_global(w0, ks * 2 + 1, lo);
+    r.h1[ks % 3] = frag_global(w1, ks * 2 + 0, lo);
+    r.l1[ks % 3] = frag_global(w1, ks * 2 + 1, lo);
 }
 __device__ __forceinline__ void lemw_ring_start(LemWideRing& r, const half8* w0, const half8* w1, unsigned lo) {
-    lemw_ring_load(r, w0, w1, lo, 0, 0);
-    lemw_ring_load(r, w0, w1, lo, 1, 1);
+    lemw_ring_load(r, w0, w1, lo, 0);
+    lemw_ring_load(r, w0, w1, lo, 1);
 }
 
 // acc0[X] = Wx0 bx[X] + W0 B0[X],  acc1[X] = Wx1 bx[X] + W1 B1[X]  over K = Wp for both node tiles (SAME: B1 = B0).
@@ -172,18 +135,18 @@ __device__ __forceinline__ void lemw_gemm2(LemWideRing& r, const half8* w0, cons
         half8 x0[M], x1[M];
 #pragma unroll
         for (int m = 0; m < M; ++m) {
-            x0[m] = lemw_gfrag(wx0, m, lo);
-            x1[m] = lemw_gfrag(wx1, m, lo);
+            x0[m] = frag_global(wx0, m, lo);
+            x1[m] = frag_global(wx1, m, lo);
         }
         const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int X = 0; X < LEMW_NT; ++X) {
-            const half8 v0 = lemw_lfrag(bx, X * M);
+            const half8 v0 = frag_lds(bx, X * M);
             acc0[X] = __builtin_amdgcn_mfma_f32_32x32x16_f16(x0[0], v0, zero, 0, 0, 0);
             acc1[X] = __builtin_amdgcn_mfma_f32_32x32x16_f16(x1[0], v0, zero, 0, 0, 0);
 #pragma unroll
             for (int m = 1; m < M; ++m) {
-                const half8 vm = lemw_lfrag(bx, X * M + m);
+                const half8 vm = frag_lds(bx, X * M + m);
                 acc0[X] = __builtin_amdgcn_mfma_f32_32x32x16_f16(x0[m], vm, acc0[X], 0, 0, 0);
                 acc1[X] = __builtin_amdgcn_mfma_f32_32x32x16_f16(x1[m], vm, acc1[X], 0, 0, 0);
             }
@@ -193,23 +156,18 @@ __device__ __forceinline__ void lemw_gemm2(LemWideRing& r, const half8* w0, cons
     for (int ks = 0; ks < KS; ++ks) {
         // fence per k-step: left alone the scheduler hoists the unrolled loop's LDS reads far ahead of their MFMAs and spills
         __builtin_amdgcn_sched_barrier(0);
-        if (ks + 2 < KS) lemw_ring_load(r, w0, w1, lo, (ks + 2) % 3, ks + 2);
+        if (ks + 2 < KS) lemw_ring_load(r, w0, w1, lo, ks + 2);
         const half8 ah0 = r.h0[ks % 3], al0 = r.l0[ks % 3], ah1 = r.h1[ks % 3], al1 = r.l1[ks % 3];
 #pragma unroll
         for (int X = 0; X < LEMW_NT; ++X) {
-            const half8 bh0 = lemw_lfrag(b0, X * FR + ks * 2 + 0), bl0 = lemw_lfrag(b0, X * FR + ks * 2 + 1);
+            const half8 bh0 = frag_lds(b0, X * FR + ks * 2 + 0), bl0 = frag_lds(b0, X * FR + ks * 2 + 1);
             half8 bh1 = bh0, bl1 = bl0;
             if (!SAME) {
-                bh1 = lemw_lfrag(b1, X * FR + ks * 2 + 0);
-                bl1 = lemw_lfrag(b1, X * FR + ks * 2 + 1);
+                bh1 = frag_lds(b1, X * FR + ks * 2 + 0);
+                bl1 = frag_lds(b1, X * FR + ks * 2 + 1);
             }
-            // three back-to-back MFMAs per accumulator, the order of mma_chunk_split
-            acc0[X] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al0, bh0, acc0[X], 0, 0, 0);
-            acc0[X] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah0, bl0, acc0[X], 0, 0, 0);
-            acc0[X] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah0, bh0, acc0[X], 0, 0, 0);
-            acc1[X] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al1, bh1, acc1[X], 0, 0, 0);
-            acc1[X] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah1, bl1, acc1[X], 0, 0, 0);
-            acc1[X] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah1, bh1, acc1[X], 0, 0, 0);
+            split_mfma3(ah0, al0, bh0, bl0, acc0[X]);
+            split_mfma3(ah1, al1, bh1, bl1, acc1[X]);
         }
     }
 }
@@ -222,10 +180,7 @@ __device__ __forceinline__ void lemw_publish(const f32x16& st, char* slice) {
         float v[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = st[8 * s + j];
-        half8 hi, lo;
-        split8(v, hi, lo);
-        *reinterpret_cast<half8*>(slice + (s * 2 + 0) * 1024) = hi;
-        *reinterpret_cast<half8*>(slice + (s * 2 + 1) * 1024) = lo;
+        publish_split<1>(v, slice, s, 0);
     }
 }
 
@@ -288,7 +243,7 @@ __global__ __launch_bounds__(64 * KT) void lem_wide_kernel(LemWideArgs a) {
     const float inv_w = uniform_ro(a.scales, 4), inv_z = uniform_ro(a.scales, 5);
     const float c0 = -inv_w * LOG2E, c1z = -2.0f * inv_w * LOG2E, c1y = -2.0f * inv_z * LOG2E, idt = 1.0f / a.dt;
 
-    // opaque per-lane offsets (see lemw_gfrag): global fragments, the y / z areas as read, this wave's slices of them as written
+    // opaque per-lane offsets (see frag_global): global fragments, the y / z areas as read, this wave's slices of them as written
     unsigned lo = lane * 16, lo_y = lane * 16 + YBASE, lo_z = lane * 16 + ZBASE;
     asm volatile("" : "+v"(lo), "+v"(lo_y), "+v"(lo_z));
     const char* const rd_y = lds + lo_y;
@@ -372,10 +327,7 @@ using namespace msmp;
 int g_lem_wide = 1;     // msmp_tune("lem_wide", 0): the host keeps the per-step GEMM + pointwise loop at widths other than 128
 
 static bool lem_wide_shape_ok(const char* who, int ninp, int width) {
-    if (width < 1 || width > LEMW_MAX_W) {
-        set_error("%s: width=%d outside 1..%d", who, width, LEMW_MAX_W);
-        return false;
-    }
+    if (!wide_width_ok(who, width)) return false;
     if (ninp < 1 || ninp > LEM_MAX_INP) {
         set_error("%s: ninp=%d outside 1..%d", who, ninp, LEM_MAX_INP);
         return false;
@@ -398,14 +350,6 @@ extern "C" int msmp_pack_lem_wide_f32(const float* weights, const float* weights
     return check_launch("pack_lem_wide_kernel");
 }
 
-template <int KT>
-static void lem_wide_launch(const LemWideArgs& a, int kt, int m, unsigned grid, hipStream_t st) {
-    if constexpr (KT < 8)
-        if (kt != KT) return lem_wide_launch<KT + 1>(a, kt, m, grid, st);
-    if (m == 1) hipLaunchKernelGGL((lem_wide_kernel<KT, 1>), dim3(grid), dim3(64 * KT), 0, st, a);
-    else hipLaunchKernelGGL((lem_wide_kernel<KT, 2>), dim3(grid), dim3(64 * KT), 0, st, a);
-}
-
 extern "C" int msmp_lem_encoder_wide_f32(const float* xin, int64_t n_nodes, int t_len, int ninp, int width, float dt, const float* packed,
                                          const float* y0, const float* z0, float* y_out, float* z_out, msmp_stream_t stream) {
     if (!lem_wide_shape_ok("msmp_lem_encoder_wide_f32", ninp, width)) return MSMP_ERR_UNSUPPORTED;
@@ -422,7 +366,11 @@ extern "C" int msmp_lem_encoder_wide_f32(const float* xin, int64_t n_nodes, int 
     const unsigned grid = (unsigned)((n_nodes + 32 * LEMW_NT - 1) / (32 * LEMW_NT));
     hipStream_t st = (hipStream_t)stream;
     timing_begin(MSMP_K_LEM, st);
-    lem_wide_launch<1>(a, kt, (3 * ninp + 2 + 15) / 16, grid, st);
+    dispatch_kt(kt, [&](auto K) {
+        constexpr int KT = decltype(K)::value;
+        if ((3 * ninp + 2 + 15) / 16 == 1) hipLaunchKernelGGL((lem_wide_kernel<KT, 1>), dim3(grid), dim3(64 * KT), 0, st, a);
+        else hipLaunchKernelGGL((lem_wide_kernel<KT, 2>), dim3(grid), dim3(64 * KT), 0, st, a);
+    });
     timing_end(MSMP_K_LEM, st);
     return check_launch("lem_wide_kernel");
 }

@@ -9,20 +9,19 @@
 //     (consecutive CSR rows) are the 2 x 32 columns of the tile's MFMAs;
 //   * per tile wave T gathers channels 32 T .. 32 T + 31 of p[target] and q[source] for all edges (16-byte loads, a full 128-byte line per
 //     edge and wave), forms Swish once per element, splits it and publishes the hi / lo B fragments in LDS as
-//     [k-step][plane][column block][lane] half8 (lane-linear: one conflict-free ds_write_b128 / ds_read_b128 per fragment);
-//   * every wave reads all B fragments: three v_mfma_f32_32x32x16_f16 per K = 16 step into one fp32 accumulator initialised with
-//     b2 2^s (mfma_tiles.h); Swish(acc 2^-s) goes to the wave's OWN message area in LDS ([edge][32 channels], row stride 36 floats) and
+//     [k-step][plane][column block][lane] half8 (wide_frags.h);
+//   * every wave reads all B fragments: three MFMAs per K = 16 step (split_mfma3) into one fp32 accumulator initialised with
+//     b2 2^s; Swish(acc 2^-s) goes to the wave's OWN message area in LDS ([edge][32 channels], row stride 36 floats) and
 //     the wave sums its 32 channels per target in CSR order in fp32 and stores them: no other wave is involved after the MFMAs;
 //   * for KT <= 6 the next tile's gathers are issued before the current tile's MFMAs and wait in registers (64 of them); above, the
 //     register file has no room beside the 16 KT weight registers and they are issued after the tile's stores.
 // A message depends on nothing but its own edge (an MFMA column) and a target's mean is a sequential fp32 sum over its CSR row, so the
 // result does not depend on how the targets are cut into tiles, on the tile slot, or on the workgroup.
 // Rows / columns W .. Wp - 1 of the packed W2 and of the bias are exact zeros: the padded channels come out as Swish(0) = 0.
-#include "mfma_tiles.h"
+#include "wide_frags.h"
 
 namespace msmp {
 
-constexpr int WMSG_MAX_W = 256;
 constexpr int WMSG_NB = 2;                    // 32-edge column blocks per tile
 constexpr int WMSG_TE = 32 * WMSG_NB;         // edges per tile = the largest in-degree the kernel takes
 constexpr int WMSG_MROW = 36;                 // floats per message row: 4 x odd, so the 16-lane groups of a 16-byte access hit 16 distinct slots
@@ -49,22 +48,10 @@ struct WideMsgPackArgs {
 
 // scales[0] = 2^s with max(|W2|, |b2|) 2^s in [16, 32), scales[4] = 2^-s
 __global__ __launch_bounds__(256) void pack_wide_msg_scale_kernel(WideMsgPackArgs a) {
-    __shared__ float red[256];
-    float m = 0.f;
-    for (int i = threadIdx.x; i < a.width * a.width; i += 256) m = fmaxf(m, fabsf(a.w2[i]));
-    for (int i = threadIdx.x; i < a.width; i += 256) m = fmaxf(m, fabsf(a.b2[i]));
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + off]);
-        __syncthreads();
-    }
-    if (threadIdx.x < 8) {
-        const float mx = red[0];
-        int e = 0;
-        if (mx > 0.f && mx < 3.0e38f) (void)frexpf(mx, &e);
-        const int sft = mx > 0.f ? 5 - e : 0;
-        a.out[threadIdx.x] = threadIdx.x == 0 ? ldexpf(1.0f, sft) : threadIdx.x == 4 ? ldexpf(1.0f, -sft) : 0.f;
+    const int sft = block_scale_shift(fmaxf(abs_max_part(a.w2, a.width * a.width), abs_max_part(a.b2, a.width)));
+    if (threadIdx.x == 0) {
+        store_scale_group(a.out, 0, sft, 0);
+        a.out[1] = a.out[3] = a.out[5] = a.out[7] = 0.f;        // (no second scale group)
     }
 }
 
@@ -74,16 +61,11 @@ __global__ void pack_wide_msg_kernel(WideMsgPackArgs a) {
     const int kt = a.kt, W = a.width;
     const int64_t tid0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t p = tid0; p < 32 * kt; p += stride) a.out[L.bias + p] = p < W ? a.b2[p] * sc : 0.f;
-    _Float16* wh = reinterpret_cast<_Float16*>(a.out + L.w);
-    const int64_t n = (int64_t)2048 * kt * kt;
-    for (int64_t p = tid0; p < n; p += stride) {
-        const int j = (int)(p & 7), lane = (int)(p >> 3) & 63, plane = (int)(p >> 9) & 1;
-        const int fr = (int)(p >> 10), ks = fr % (2 * kt), T = fr / (2 * kt);
+    pack_split_fragments(reinterpret_cast<_Float16*>(a.out + L.w), (int64_t)2 * kt * kt, [&](int fr, int lane, int j) {
+        const int ks = fr % (2 * kt), T = fr / (2 * kt);
         const int row = 32 * T + (lane & 31), k = split_k_natural(ks, lane >> 5, j);
-        const float w = row < W && k < W ? a.w2[(size_t)row * W + k] * sc : 0.f;
-        const _Float16 hi = (_Float16)w;
-        wh[p] = plane == 0 ? hi : (_Float16)(w - (float)hi);
-    }
+        return row < W && k < W ? a.w2[(size_t)row * W + k] * sc : 0.f;
+    });
 }
 
 struct WideMsgArgs {
@@ -157,8 +139,8 @@ __device__ __forceinline__ void wmsg_gather(const WideMsgArgs& a, const WideMsgT
 #pragma unroll
         for (int ss = 0; ss < 2; ++ss) {
             const int k0 = 16 * (2 * T + ss) + 8 * hh;
-            const int ka = min(k0, ld - 4), kb = min(k0 + 4, ld - 4);
             WideMsgItem& it = g[ss * WMSG_NB + nb];
+            const int ka = min(k0, ld - 4), kb = min(k0 + 4, ld - 4);
             it.p0 = *reinterpret_cast<const f32x4*>(pr[nb] + ka);
             it.p1 = *reinterpret_cast<const f32x4*>(pr[nb] + kb);
             it.q0 = *reinterpret_cast<const f32x4*>(qr[nb] + ka);
@@ -166,9 +148,7 @@ __device__ __forceinline__ void wmsg_gather(const WideMsgArgs& a, const WideMsgT
         }
 }
 
-// Swish(p + q) of the gathered items -> hi / lo B fragments of the tile: fragment (k-step s, plane, block nb) at ((2 s + plane) NB + nb) KB.
-// `worst` collects the largest |activation| as an integer (the bit patterns of non-negative floats order like their values, NaN above
-// Inf): compared against NODE_RANGE once, after the last tile -- the predicate of out_of_range at two integer operations per value
+// Swish(p + q) of the gathered items -> hi / lo B fragments of the tile (publish_split); `worst`: the largest |activation| (track_abs_max)
 template <int KT>
 __device__ __forceinline__ void wmsg_publish(const WideMsgArgs& a, int ne, int T, int c, int hh, const WideMsgItem (&g)[2 * WMSG_NB],
                                              char* b_lane, unsigned& worst) {
@@ -182,12 +162,9 @@ __device__ __forceinline__ void wmsg_publish(const WideMsgArgs& a, int ne, int T
         for (int j = 0; j < 8; ++j) {
             const float x = j < 4 ? g[i].p0[j] + g[i].q0[j] : g[i].p1[j - 4] + g[i].q1[j - 4];
             v[j] = swishf(live && k0 + j < a.width ? x : 0.f);
-            worst = max(worst, __float_as_uint(v[j]) & 0x7fffffffu);
+            track_abs_max(worst, v[j]);
         }
-        half8 hi, lo;
-        split8(v, hi, lo);
-        *reinterpret_cast<half8*>(b_lane + ((2 * s + 0) * WMSG_NB + nb) * 1024) = hi;
-        *reinterpret_cast<half8*>(b_lane + ((2 * s + 1) * WMSG_NB + nb) * 1024) = lo;
+        publish_split<WMSG_NB>(v, b_lane, s, nb);
         // one item at a time, its maximum taken here: left alone the compiler sinks the 32 maxima of a tile to the end of the tile loop and
         // keeps the 32 activations in registers across the MFMAs for it
         asm volatile("" : "+v"(worst));
@@ -241,25 +218,15 @@ __global__ __launch_bounds__(64 * KT, 2) void wide_message_kernel(WideMsgArgs a)
         if (PREFETCH && more) wmsg_gather<KT>(a, nxt, map_next, T, c, hh, g);
 
         f32x16 acc[NB];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 bv = *reinterpret_cast<const f32x4*>(bias + 8 * q);
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) acc[nb][4 * q + m] = bv[m];
-        }
+        acc_bias_init(bias, acc);
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             // fence per k-step: left alone the scheduler hoists the unrolled loop's LDS reads far ahead of their MFMAs
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) {
-                const half8 bh = *reinterpret_cast<const half8*>(b_lane + ((2 * ks + 0) * NB + nb) * 1024);
-                const half8 bl = *reinterpret_cast<const half8*>(b_lane + ((2 * ks + 1) * NB + nb) * 1024);
-                acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[ks], bh, acc[nb], 0, 0, 0);
-                acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[ks], bl, acc[nb], 0, 0, 0);
-                acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[ks], bh, acc[nb], 0, 0, 0);
+                const half8 bh = frag_lds(b_lane, (2 * ks + 0) * NB + nb), bl = frag_lds(b_lane, (2 * ks + 1) * NB + nb);
+                split_mfma3(ah[ks], al[ks], bh, bl, acc[nb]);
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -301,7 +268,7 @@ __global__ __launch_bounds__(64 * KT, 2) void wide_message_kernel(WideMsgArgs a)
         if (!PREFETCH && more) wmsg_gather<KT>(a, nxt, map_next, T, c, hh, g);
         cur = nxt;
     }
-    if (worst > __float_as_uint(NODE_RANGE)) status_raise(a.status, MSMP_STATUS_NODE_SATURATED);
+    if (node_range_exceeded(worst)) status_raise(a.status, MSMP_STATUS_NODE_SATURATED);
 }
 
 }  // namespace msmp
@@ -310,21 +277,13 @@ using namespace msmp;
 
 int g_wide_msg = 1;     // msmp_tune("wide_msg", 0): the host layer keeps gather + row GEMM + scatter at widths other than 128
 
-static bool wide_msg_width_ok(const char* who, int width) {
-    if (width < 1 || width > WMSG_MAX_W) {
-        set_error("%s: width=%d outside 1..%d", who, width, WMSG_MAX_W);
-        return false;
-    }
-    return true;
-}
-
 extern "C" int64_t msmp_packed_wide_msg_floats(int width) {
-    if (!wide_msg_width_ok("msmp_packed_wide_msg_floats", width)) return 0;
+    if (!wide_width_ok("msmp_packed_wide_msg_floats", width)) return 0;
     return wide_msg_layout((width + 31) / 32).total;
 }
 
 extern "C" int msmp_pack_wide_msg_f32(const float* w2, const float* b2, int width, float* packed_out, msmp_stream_t stream) {
-    if (!wide_msg_width_ok("msmp_pack_wide_msg_f32", width)) return MSMP_ERR_ARG;
+    if (!wide_width_ok("msmp_pack_wide_msg_f32", width)) return MSMP_ERR_ARG;
     MSMP_REQUIRE(w2 && b2 && packed_out, MSMP_ERR_ARG, "msmp_pack_wide_msg_f32: null pointer");
     WideMsgPackArgs a{w2, b2, width, (width + 31) / 32, packed_out};
     hipLaunchKernelGGL(pack_wide_msg_scale_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
@@ -333,26 +292,13 @@ extern "C" int msmp_pack_wide_msg_f32(const float* w2, const float* b2, int widt
 }
 
 extern "C" int msmp_wide_message_max_in_degree(int width) {
-    if (!wide_msg_width_ok("msmp_wide_message_max_in_degree", width)) return 0;
+    if (!wide_width_ok("msmp_wide_message_max_in_degree", width)) return 0;
     return WMSG_TE;
-}
-
-template <int KT>
-static void wide_message_launch(const WideMsgArgs& a, int kt, int cus, hipStream_t st) {
-    if constexpr (KT < 8)
-        if (kt != KT) return wide_message_launch<KT + 1>(a, kt, cus, st);
-    // persistent: as many workgroups as are resident at once (LDS: 8 KT KB of fragments + 9 KT KB of messages)
-    constexpr int lds_bytes = 2 * KT * 2 * WMSG_NB * 1024 + KT * WMSG_TE * WMSG_MROW * 4 + 32 * KT * 4 + 3 * WMSG_MAP_INTS * 4;
-    constexpr int by_lds = 160 * 1024 / lds_bytes, by_waves = 8 / KT;       // two waves per SIMD at up to 256 registers
-    constexpr int per_cu = by_lds < by_waves ? (by_lds < 1 ? 1 : by_lds) : (by_waves < 1 ? 1 : by_waves);
-    const long resident = (long)cus * per_cu;
-    const unsigned grid = (unsigned)(a.n_tiles < resident ? a.n_tiles : resident);
-    hipLaunchKernelGGL((wide_message_kernel<KT>), dim3(grid), dim3(64 * KT), 0, st, a);
 }
 
 extern "C" int msmp_wide_message_f32(const float* p, const float* q, const int32_t* rowptr, const int32_t* col, int64_t n_nodes, int64_t n_edges,
                                      int max_in_degree, int width, int ld, const float* packed, float* agg_out, msmp_stream_t stream) {
-    if (!wide_msg_width_ok("msmp_wide_message_f32", width)) return MSMP_ERR_ARG;
+    if (!wide_width_ok("msmp_wide_message_f32", width)) return MSMP_ERR_ARG;
     MSMP_REQUIRE(ld >= width && ld % 4 == 0 && ld <= 4096, MSMP_ERR_ARG, "msmp_wide_message_f32: ld=%d is not a multiple of 4 in width..4096", ld);
     MSMP_REQUIRE(p && q && rowptr && col && packed && agg_out, MSMP_ERR_ARG, "msmp_wide_message_f32: null pointer");
     MSMP_REQUIRE(n_nodes >= 0 && n_nodes < (1L << 31) && n_edges >= 0 && n_edges < (1L << 31) && max_in_degree >= 0, MSMP_ERR_ARG,
@@ -375,8 +321,13 @@ extern "C" int msmp_wide_message_f32(const float* p, const float* q, const int32
     const long n_tiles = (n_nodes + tile_nodes - 1) / tile_nodes;
     WideMsgArgs a{p, q, rowptr, col, (int)n_nodes, tile_nodes, (int)n_tiles, width, ld, packed + L.scales, packed + L.bias,
                   reinterpret_cast<const half8*>(packed + L.w), agg_out, status_ptr()};
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    wide_message_launch<1>(a, kt, cus, st);
+    dispatch_kt(kt, [&](auto K) {
+        constexpr int KT = decltype(K)::value;
+        // persistent (LDS: 8 KT KB of fragments + 9 KT KB of messages + bias + maps)
+        constexpr int lds_bytes = 2 * KT * 2 * WMSG_NB * 1024 + KT * WMSG_TE * WMSG_MROW * 4 + 32 * KT * 4 + 3 * WMSG_MAP_INTS * 4;
+        const long resident = resident_workgroups(device_cus(), lds_bytes, KT);
+        const unsigned grid = (unsigned)(a.n_tiles < resident ? a.n_tiles : resident);
+        hipLaunchKernelGGL((wide_message_kernel<KT>), dim3(grid), dim3(64 * KT), 0, st, a);
+    });
     return check_launch("wide_message_kernel");
 }

@@ -17,18 +17,16 @@
 //     K = 2 Wp + 16, Swish(z) is published as B fragments over the agg area (it is dead by then), and GEMM 2 accumulates y into the
 //     registers that wait for the statistics: 16 per column block, 64 per head, 128 for a gated pair;
 //   * the weights stream: an A fragment (row slice T, k-step) has exactly one consumer wave, so it goes from L2 into that wave's
-//     registers through a three-slot ring (lem_wide_kernel.hip) and serves the two column blocks of the pair.  Sharing a pass over the
+//     registers through a three-slot ring (as in lem_wide_kernel.hip) and serves the two column blocks of the pair.  Sharing a pass over the
 //     weights among all four blocks would halve the L2 traffic but needs 64 more accumulator registers for z beside the 128 of y
 //     and K-chunked staging of every operand; with two blocks the stream is 2 KB per wave and k-step against six MFMAs.
-// Arithmetic of the default path (mfma_tiles.h): node rows scaled by 2^8 and split (split8_node), weights pre-multiplied by a power of
-// two at pack time, three v_mfma_f32_32x32x16_f16 per K = 16 step into one fp32 accumulator initialised with the scaled bias.
+// Arithmetic of wide_frags.h, with the node rows scaled by 2^8 and split (split8_node) and the accumulators initialised with the scaled bias.
 // Rows / columns W .. Wp - 1 of the packed weights and biases are exact zeros.  One workgroup per graph and fixed-order sums: the result
 // of a graph does not depend on the batch around it, on its position, or on the run.
-#include "mfma_tiles.h"
+#include "wide_frags.h"
 
 namespace msmp {
 
-constexpr int WNT_MAX_W = 256;
 constexpr int WNT_MAX_NODES = 128;            // four 32-node column blocks
 constexpr int WNT_NB = 2;                     // column blocks that share one pass over the weights
 
@@ -59,29 +57,9 @@ struct WideTailPackArgs {
 // block 0: (W3, b3), block 1: (W4, b4): scales[i] = 2^s with max(|M|, |b|) 2^s in [16, 32); scales[4] = 2^-(s3 + 8) (the node rows carry
 // 2^8), scales[5] = 2^-s4.  grid = 2.
 __global__ __launch_bounds__(256) void pack_wide_tail_scale_kernel(WideTailPackArgs a) {
-    __shared__ float red[256];
     const int n_w = blockIdx.x == 0 ? a.width * (2 * a.width + a.nv) : a.width * a.width;
-    const float* w = blockIdx.x == 0 ? a.w3 : a.w4;
-    const float* b = blockIdx.x == 0 ? a.b3 : a.b4;
-    float m = 0.f;
-    for (int i = threadIdx.x; i < n_w; i += 256) m = fmaxf(m, fabsf(w[i]));
-    for (int i = threadIdx.x; i < a.width; i += 256) m = fmaxf(m, fabsf(b[i]));
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + off]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const float mx = red[0];
-        int e = 0;
-        if (mx > 0.f && mx < 3.0e38f) (void)frexpf(mx, &e);
-        const int sft = mx > 0.f ? 5 - e : 0;
-        a.out[blockIdx.x] = ldexpf(1.0f, sft);
-        a.out[4 + blockIdx.x] = ldexpf(1.0f, -sft - (blockIdx.x == 0 ? 8 : 0));
-        a.out[2 + blockIdx.x] = 0.f;
-        a.out[6 + blockIdx.x] = 0.f;
-    }
+    const int sft = block_scale_shift(fmaxf(abs_max_part(blockIdx.x == 0 ? a.w3 : a.w4, n_w), abs_max_part(blockIdx.x == 0 ? a.b3 : a.b4, a.width)));
+    if (threadIdx.x == 0) store_scale_group(a.out, blockIdx.x, sft, blockIdx.x == 0 ? 8 : 0);
 }
 
 __global__ void pack_wide_tail_kernel(WideTailPackArgs a) {
@@ -93,11 +71,8 @@ __global__ void pack_wide_tail_kernel(WideTailPackArgs a) {
         a.out[L.b3 + p] = p < W ? a.b3[p] * s3 * 256.0f : 0.f;
         a.out[L.b4 + p] = p < W ? a.b4[p] * s4 : 0.f;
     }
-    _Float16* w3h = reinterpret_cast<_Float16*>(a.out + L.w3);
-    const int64_t n3 = (int64_t)1024 * kt * k1s;
-    for (int64_t p = tid0; p < n3; p += stride) {
-        const int j = (int)(p & 7), lane = (int)(p >> 3) & 63, plane = (int)(p >> 9) & 1;
-        const int fr = (int)(p >> 10), ks = fr % k1s, T = fr / k1s;
+    pack_split_fragments(reinterpret_cast<_Float16*>(a.out + L.w3), (int64_t)kt * k1s, [&](int fr, int lane, int j) {
+        const int ks = fr % k1s, T = fr / k1s;
         const int row = 32 * T + (lane & 31), hh = lane >> 5;
         int col = -1;
         if (ks < 4 * kt) {
@@ -105,20 +80,13 @@ __global__ void pack_wide_tail_kernel(WideTailPackArgs a) {
             if (k < W) col = part * W + k;
         } else if (hh == 0 && j < nv)
             col = 2 * W + j;
-        const float w = row < W && col >= 0 ? a.w3[(size_t)row * kin + col] * s3 : 0.f;
-        const _Float16 hi = (_Float16)w;
-        w3h[p] = plane == 0 ? hi : (_Float16)(w - (float)hi);
-    }
-    _Float16* w4h = reinterpret_cast<_Float16*>(a.out + L.w4);
-    const int64_t n4 = (int64_t)2048 * kt * kt;
-    for (int64_t p = tid0; p < n4; p += stride) {
-        const int j = (int)(p & 7), lane = (int)(p >> 3) & 63, plane = (int)(p >> 9) & 1;
-        const int fr = (int)(p >> 10), ks = fr % (2 * kt), T = fr / (2 * kt);
+        return row < W && col >= 0 ? a.w3[(size_t)row * kin + col] * s3 : 0.f;
+    });
+    pack_split_fragments(reinterpret_cast<_Float16*>(a.out + L.w4), (int64_t)2 * kt * kt, [&](int fr, int lane, int j) {
+        const int ks = fr % (2 * kt), T = fr / (2 * kt);
         const int row = 32 * T + (lane & 31), k = 32 * (ks >> 1) + split_k_acc(ks & 1, lane >> 5, j);
-        const float w = row < W && k < W ? a.w4[(size_t)row * W + k] * s4 : 0.f;
-        const _Float16 hi = (_Float16)w;
-        w4h[p] = plane == 0 ? hi : (_Float16)(w - (float)hi);
-    }
+        return row < W && k < W ? a.w4[(size_t)row * W + k] * s4 : 0.f;
+    });
 }
 
 struct WideTailHead {
@@ -138,21 +106,16 @@ struct WideTailArgs {
     int* status;
 };
 
-// the A fragments in flight: slot ks % 3 holds k-step ks
+// the A fragments in flight (two k-steps ahead of their MFMAs): slot ks % 3 holds k-step ks
 struct WideTailRing {
     half8 h[3], l[3];
 };
-
-// (a wave-uniform base + ONE opaque per-lane byte offset + a compile-time constant: see lemw_gfrag of lem_wide_kernel.hip)
-__device__ __forceinline__ half8 wnt_gfrag(const half8* base, int frag, unsigned lo) {
-    return *reinterpret_cast<const half8*>(reinterpret_cast<const char*>(base + frag * 64) + lo);
-}
 __device__ __forceinline__ void wnt_ring_start(WideTailRing& r, const half8* w, unsigned lo, int nks) {
-    r.h[0] = wnt_gfrag(w, 0, lo);
-    r.l[0] = wnt_gfrag(w, 1, lo);
+    r.h[0] = frag_global(w, 0, lo);
+    r.l[0] = frag_global(w, 1, lo);
     if (nks > 1) {
-        r.h[1] = wnt_gfrag(w, 2, lo);
-        r.l[1] = wnt_gfrag(w, 3, lo);
+        r.h[1] = frag_global(w, 2, lo);
+        r.l[1] = frag_global(w, 3, lo);
     }
 }
 
@@ -165,36 +128,22 @@ __device__ __forceinline__ void wnt_gemm(WideTailRing& r, const half8* w, unsign
         // fence per k-step: left alone the scheduler hoists the unrolled loop's LDS reads far ahead of their MFMAs
         __builtin_amdgcn_sched_barrier(0);
         if (ks + 2 < NKS) {
-            r.h[(ks + 2) % 3] = wnt_gfrag(w, (ks + 2) * 2 + 0, lo);
-            r.l[(ks + 2) % 3] = wnt_gfrag(w, (ks + 2) * 2 + 1, lo);
+            r.h[(ks + 2) % 3] = frag_global(w, (ks + 2) * 2 + 0, lo);
+            r.l[(ks + 2) % 3] = frag_global(w, (ks + 2) * 2 + 1, lo);
         }
         const half8 ah = r.h[ks % 3], al = r.l[ks % 3];
 #pragma unroll
         for (int blk = 0; blk < WNT_NB; ++blk) {
-            const half8 bh = *reinterpret_cast<const half8*>(b_lane + ((ks * 2 + 0) * WNT_NB + blk) * 1024);
-            const half8 bl = *reinterpret_cast<const half8*>(b_lane + ((ks * 2 + 1) * WNT_NB + blk) * 1024);
-            acc[blk] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[blk], 0, 0, 0);
-            acc[blk] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[blk], 0, 0, 0);
-            acc[blk] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[blk], 0, 0, 0);
+            const half8 bh = frag_lds(b_lane, (ks * 2 + 0) * WNT_NB + blk), bl = frag_lds(b_lane, (ks * 2 + 1) * WNT_NB + blk);
+            split_mfma3(ah, al, bh, bl, acc[blk]);
         }
     }
     __builtin_amdgcn_sched_barrier(0);
 }
 
-__device__ __forceinline__ void wnt_acc_bias(const float* bias, int T, int hh, f32x16 (&acc)[WNT_NB]) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const f32x4 bv = *reinterpret_cast<const f32x4*>(bias + 32 * T + 8 * q + 4 * hh);
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int blk = 0; blk < WNT_NB; ++blk) acc[blk][4 * q + m] = bv[m];
-    }
-}
-
 // wave T's share of a pair's rows of `src` ([N, ld]: h or agg): k-steps 2 T, 2 T + 1 of both column blocks (a 128-byte line per node and
 // wave) -> hi / lo B fragments scaled by 2^8 at area_lane + ((k-step 2 + plane) NB + block) KB.  Every address is clamped into the tensor;
-// dead nodes (local index >= cnt) and channels >= W become zeros.  `worst`: the largest |value| as an integer (see wmsg_publish).
+// dead nodes (local index >= cnt) and channels >= W become zeros.  `worst`: the largest |value| (track_abs_max).
 __device__ __forceinline__ void wnt_stage_rows(const float* src, int ld, int W, int n0, int n_nodes, int cnt, int pbase, int T, int c, int hh,
                                                char* area_lane, unsigned& worst) {
     f32x4 v0[2 * WNT_NB], v1[2 * WNT_NB];
@@ -218,12 +167,9 @@ __device__ __forceinline__ void wnt_stage_rows(const float* src, int ld, int W, 
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             x[j] = live && k0 + j < W ? (j < 4 ? v0[i][j] : v1[i][j - 4]) : 0.f;
-            worst = max(worst, __float_as_uint(x[j]) & 0x7fffffffu);
+            track_abs_max(worst, x[j]);
         }
-        half8 hi, lo;
-        split8_node(x, hi, lo);
-        *reinterpret_cast<half8*>(area_lane + ((2 * s + 0) * WNT_NB + blk) * 1024) = hi;
-        *reinterpret_cast<half8*>(area_lane + ((2 * s + 1) * WNT_NB + blk) * 1024) = lo;
+        publish_split<WNT_NB, true>(x, area_lane, s, blk);
     }
 }
 
@@ -292,7 +238,7 @@ __device__ __forceinline__ void wnt_head_pair(const WideTailArgs& a, const WideT
     wnt_stage_rows(hd.agg, a.ld, a.width, n0, a.n_nodes, cnt, pbase, T, c, hh, lds + HB + lane * 16, worst);
     wnt_stage_vars(a, n0, cnt, pbase, lds + HB + KS * 2 * WNT_NB * 1024, tid, 64 * KT);
     f32x16 z[WNT_NB];
-    wnt_acc_bias(hd.b3, T, hh, z);
+    acc_bias_init(hd.b3 + 32 * T + 4 * hh, z);
     __syncthreads();                // the pair's h, agg and variables fragments are complete
     wnt_gemm<2 * KS + 1>(ring, w3, lo, lds + lane * 16, z);
     wnt_ring_start(ring, w4, lo, KS);
@@ -305,15 +251,12 @@ __device__ __forceinline__ void wnt_head_pair(const WideTailArgs& a, const WideT
             float v[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = swishf(z[blk][8 * s + j] * inv3);
-            half8 hi, lw;
-            split8(v, hi, lw);
-            *reinterpret_cast<half8*>(lds + HB + lane * 16 + (((2 * T + s) * 2 + 0) * WNT_NB + blk) * 1024) = hi;
-            *reinterpret_cast<half8*>(lds + HB + lane * 16 + (((2 * T + s) * 2 + 1) * WNT_NB + blk) * 1024) = lw;
+            publish_split<WNT_NB>(v, lds + HB + lane * 16, 2 * T + s, blk);
         }
         __builtin_amdgcn_sched_barrier(0);      // (one column block's activations at a time)
     }
     f32x16 y[WNT_NB];
-    wnt_acc_bias(hd.b4, T, hh, y);
+    acc_bias_init(hd.b4 + 32 * T + 4 * hh, y);
     __syncthreads();                // z is complete
     wnt_gemm<KS>(ring, w4, lo, lds + HB + lane * 16, y);
     __syncthreads();                // every wave has read z: the next agg rows may be staged over it
@@ -401,7 +344,7 @@ __global__ __launch_bounds__(64 * KT, 2) void wide_node_tail_kernel(WideTailArgs
                 *reinterpret_cast<f32x4*>(a.out + (size_t)(n0 + i / extra) * ld + 32 * KT + 4 * (i % extra)) = zero;
         }
     }
-    if (worst > __float_as_uint(NODE_RANGE)) status_raise(a.status, MSMP_STATUS_NODE_SATURATED);
+    if (node_range_exceeded(worst)) status_raise(a.status, MSMP_STATUS_NODE_SATURATED);
     if (bad) status_raise(a.status, MSMP_STATUS_NONFINITE);
 }
 
@@ -414,13 +357,6 @@ using namespace msmp;
 // the node half misses the bar of test_full_depth_vs_oracle that the bf16x3 row GEMMs meet (profiles/r10a_glu_wide_node_tail.md)
 int g_wide_tail = 0;
 
-static bool wide_tail_width_ok(const char* who, int width) {
-    if (width < 1 || width > WNT_MAX_W) {
-        set_error("%s: width=%d outside 1..%d", who, width, WNT_MAX_W);
-        return false;
-    }
-    return true;
-}
 static bool wide_tail_nv_ok(const char* who, int nv) {
     if (nv < 0 || nv > MSMP_MAX_VARS) {
         set_error("%s: nv=%d outside 0..%d", who, nv, MSMP_MAX_VARS);
@@ -430,13 +366,13 @@ static bool wide_tail_nv_ok(const char* who, int nv) {
 }
 
 extern "C" int64_t msmp_packed_wide_tail_floats(int width, int nv) {
-    if (!wide_tail_width_ok("msmp_packed_wide_tail_floats", width) || !wide_tail_nv_ok("msmp_packed_wide_tail_floats", nv)) return 0;
+    if (!wide_width_ok("msmp_packed_wide_tail_floats", width) || !wide_tail_nv_ok("msmp_packed_wide_tail_floats", nv)) return 0;
     return wide_tail_layout((width + 31) / 32).total;
 }
 
 extern "C" int msmp_pack_wide_tail_f32(const float* w3, const float* b3, const float* w4, const float* b4, int width, int nv, float* packed_out,
                                        msmp_stream_t stream) {
-    if (!wide_tail_width_ok("msmp_pack_wide_tail_f32", width) || !wide_tail_nv_ok("msmp_pack_wide_tail_f32", nv)) return MSMP_ERR_ARG;
+    if (!wide_width_ok("msmp_pack_wide_tail_f32", width) || !wide_tail_nv_ok("msmp_pack_wide_tail_f32", nv)) return MSMP_ERR_ARG;
     MSMP_REQUIRE(w3 && b3 && w4 && b4 && packed_out, MSMP_ERR_ARG, "msmp_pack_wide_tail_f32: null pointer");
     WideTailPackArgs a{w3, b3, w4, b4, width, nv, (width + 31) / 32, packed_out};
     hipLaunchKernelGGL(pack_wide_tail_scale_kernel, dim3(2), dim3(256), 0, (hipStream_t)stream, a);
@@ -445,27 +381,14 @@ extern "C" int msmp_pack_wide_tail_f32(const float* w3, const float* b3, const f
 }
 
 extern "C" int msmp_wide_node_tail_max_graph_nodes(int width) {
-    if (!wide_tail_width_ok("msmp_wide_node_tail_max_graph_nodes", width)) return 0;
+    if (!wide_width_ok("msmp_wide_node_tail_max_graph_nodes", width)) return 0;
     return WNT_MAX_NODES;
-}
-
-template <int KT>
-static void wide_node_tail_launch(const WideTailArgs& a, int kt, int cus, hipStream_t st) {
-    if constexpr (KT < 8)
-        if (kt != KT) return wide_node_tail_launch<KT + 1>(a, kt, cus, st);
-    // persistent: as many workgroups as are resident at once (LDS: 16 KT + 4 KB of fragments)
-    constexpr int lds_bytes = (4 * KT + 1) * 2 * WNT_NB * 1024;
-    constexpr int by_lds = 160 * 1024 / lds_bytes, by_waves = 8 / KT;       // two waves per SIMD at up to 256 registers
-    constexpr int per_cu = by_lds < by_waves ? (by_lds < 1 ? 1 : by_lds) : (by_waves < 1 ? 1 : by_waves);
-    const long resident = (long)cus * per_cu;
-    const unsigned grid = (unsigned)(a.n_graphs < resident ? a.n_graphs : resident);
-    hipLaunchKernelGGL((wide_node_tail_kernel<KT>), dim3(grid), dim3(64 * KT), 0, st, a);
 }
 
 extern "C" int msmp_wide_node_tail_f32(const float* h, const float* agg_main, const float* agg_gate, const float* vars, const int32_t* graph_ptr,
                                        int64_t n_nodes, int64_t n_graphs, int max_graph_nodes, int nv, int width, int ld, const float* packed_main,
                                        const float* packed_gate, float eps, float* out, msmp_stream_t stream) {
-    if (!wide_tail_width_ok("msmp_wide_node_tail_f32", width)) return MSMP_ERR_UNSUPPORTED;
+    if (!wide_width_ok("msmp_wide_node_tail_f32", width)) return MSMP_ERR_UNSUPPORTED;
     if (!wide_tail_nv_ok("msmp_wide_node_tail_f32", nv)) return MSMP_ERR_ARG;
     MSMP_REQUIRE(ld >= width && ld % 4 == 0 && ld <= 4096, MSMP_ERR_ARG, "msmp_wide_node_tail_f32: ld=%d is not a multiple of 4 in width..4096", ld);
     MSMP_REQUIRE(h && agg_main && (vars || nv == 0) && graph_ptr && packed_main && out, MSMP_ERR_ARG, "msmp_wide_node_tail_f32: null pointer");
@@ -489,8 +412,11 @@ extern "C" int msmp_wide_node_tail_f32(const float* h, const float* agg_main, co
     };
     WideTailArgs a{h, vars, graph_ptr, (int)n_nodes, (int)n_graphs, nv, width, ld, eps, head(agg_main, packed_main), head(agg_gate, packed_gate), out,
                    status_ptr()};
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    wide_node_tail_launch<1>(a, kt, cus, (hipStream_t)stream);
+    dispatch_kt(kt, [&](auto K) {
+        constexpr int KT = decltype(K)::value;
+        const long resident = resident_workgroups(device_cus(), (4 * KT + 1) * 2 * WNT_NB * 1024, KT);       // persistent (LDS: 16 KT + 4 KB of fragments)
+        const unsigned grid = (unsigned)(a.n_graphs < resident ? a.n_graphs : resident);
+        hipLaunchKernelGGL((wide_node_tail_kernel<KT>), dim3(grid), dim3(64 * KT), 0, (hipStream_t)stream, a);
+    });
     return check_launch("wide_node_tail_kernel");
 }

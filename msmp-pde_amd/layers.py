@@ -93,12 +93,7 @@ class _MPLayerBase(nn.Module):
         self.message_net_2 = nn.Sequential(_linear(hidden_features, hidden_features), Swish())
         self.update_net_1 = nn.Sequential(_linear(in_features + hidden_features + n_variables, hidden_features), Swish())
         self._make_update_net_2(hidden_features, out_features)
-        self._packed = None
-        self._packed_key = None
-        self._wide_msg = None
-        self._wide_msg_key = None
-        self._wide_tail = None
-        self._wide_tail_key = None
+        self._packed, self._wide_w, self._wide_msg, self._wide_tail = (_lib.PackedCache() for _ in range(4))
         self._ps = None
 
     def _params8(self):
@@ -114,34 +109,29 @@ class _MPLayerBase(nn.Module):
         if self.wide:
             raise _lib.MsmpError(f'the packed layer blob exists for hidden width {HIDDEN} only')
         ps = self._params8()
-        key = (_lib.PARAM_EPOCH[0], ps[0].data_ptr(), ps[7].data_ptr(), ps[0].dtype) + tuple(p._version for p in ps)
-        if key != self._packed_key:
-            dev = ps[0].device
-            if dev.type != 'cuda' or any(p.device != dev for p in ps):
-                raise _lib.MsmpError('layer parameters must be on the GPU (HIP path only, no CPU fallback)')
+
+        def build():
             L = lib()
-            n = L.msmp_packed_layer_floats(self.time_window, self.n_variables)
-            blob = torch.empty(n, dtype=torch.float32, device=dev)
-            f = [p.detach().to(torch.float32).contiguous() for p in ps]
+            blob = torch.empty(L.msmp_packed_layer_floats(self.time_window, self.n_variables), dtype=torch.float32, device=ps[0].device)
+            f = [_f32c(p) for p in ps]
             check(L.msmp_pack_layer_f32(*[ptr(t) for t in f], self.time_window, self.n_variables, ptr(blob),
                                         current_stream()), 'msmp_pack_layer_f32')
-            self._packed, self._packed_key = blob, key
-        return self._packed
+            return blob
+        return self._packed.get(ps, build)
 
     def wide_weights(self):
         """The wide path's operands, cached per parameter version: message_net_1 factorised per node (models_gnn.py:132-138):
         P = Wp [h | u | pos | vars] + b1 for the edge's target, Q = Wq [h | u | pos | vars] for its source, with
         Wp = [W1[:, :W] | W1[:, 2W:]], Wq = [W1[:, W:2W] | -W1[:, 2W:2W+tw+1] | 0]."""
         ps = self._params8()
-        key = (_lib.PARAM_EPOCH[0],) + tuple((p.data_ptr(), p._version) for p in ps)
-        if key != self._packed_key:
+
+        def build():
             w1 = ps[0].detach().to(torch.float32)
             W, tw = self.hidden_features, self.time_window
             wp = torch.cat((w1[:, :W], w1[:, 2 * W:]), 1).contiguous()
             wq = torch.cat((w1[:, W:2 * W], -w1[:, 2 * W:2 * W + tw + 1], torch.zeros_like(w1[:, 2 * W + tw + 1:])), 1).contiguous()
-            self._packed = (wp, wq) + tuple(p.detach().to(torch.float32).contiguous() for p in ps[1:])
-            self._packed_key = key
-        return self._packed
+            return (wp, wq) + tuple(_f32c(p) for p in ps[1:])
+        return self._wide_w.get(ps, build)
 
     def wide_message_blob(self):
         """message_net_2 in the layout of the fused wide message kernel (msmp_pack_wide_msg_f32: fp16 hi / lo fragments of W2 2^s, bias 2^s),
@@ -152,15 +142,13 @@ class _MPLayerBase(nn.Module):
         if n_floats <= 0:
             return None
         w2, b2 = self._params8()[2:4]
-        key = (_lib.PARAM_EPOCH[0], w2.data_ptr(), w2._version, b2.data_ptr(), b2._version)
-        if key != self._wide_msg_key:
-            if w2.device.type != 'cuda' or b2.device != w2.device:
-                raise _lib.MsmpError('layer parameters must be on the GPU (HIP path only, no CPU fallback)')
+
+        def build():
             blob = torch.empty(n_floats, dtype=torch.float32, device=w2.device)
             f = [_f32c(w2), _f32c(b2)]
             check(L.msmp_pack_wide_msg_f32(ptr(f[0]), ptr(f[1]), W, ptr(blob), current_stream()), 'msmp_pack_wide_msg_f32')
-            self._wide_msg, self._wide_msg_key = blob, key
-        return self._wide_msg
+            return blob
+        return self._wide_msg.get((w2, b2), build)
 
     def wide_tail_blob(self):
         """update_net_1 / update_net_2 in the layout of the fused wide node tail (msmp_pack_wide_tail_f32: fp16 hi / lo fragments of W3 2^s3 and
@@ -172,16 +160,14 @@ class _MPLayerBase(nn.Module):
         if n_floats <= 0:
             return None
         ps = self._params8()[4:8]
-        key = (_lib.PARAM_EPOCH[0],) + tuple((p.data_ptr(), p._version) for p in ps)
-        if key != self._wide_tail_key:
-            if ps[0].device.type != 'cuda' or any(p.device != ps[0].device for p in ps):
-                raise _lib.MsmpError('layer parameters must be on the GPU (HIP path only, no CPU fallback)')
+
+        def build():
             blob = torch.empty(n_floats, dtype=torch.float32, device=ps[0].device)
             f = [_f32c(p) for p in ps]
             check(L.msmp_pack_wide_tail_f32(ptr(f[0]), ptr(f[1]), ptr(f[2]), ptr(f[3]), W, nv, ptr(blob), current_stream()),
                   'msmp_pack_wide_tail_f32')
-            self._wide_tail, self._wide_tail_key = blob, key
-        return self._wide_tail
+            return blob
+        return self._wide_tail.get(ps, build)
 
     def forward(self, x, u, pos, variables, edge_index, batch, structure=None):
         """Same signature as the reference's layer forward (experiments/models_gnn.py:61-67 / 124-130);
@@ -209,6 +195,15 @@ class GNN_LayerLin(_MPLayerBase):
 
 def _f32c(t):
     return t.detach().to(torch.float32).contiguous()
+
+
+def _wide_fused(*keys):
+    """True while every switch of the fused width-generic path is on: "wide_msg", "split", "lem_wide" and the given further keys.
+    (msmp_tune("lem_wide", 0) selects the unfused width-generic path as a WHOLE: the model is then independent of "split", bitwise the
+    exact-fp32 evaluation, which is what that setting is compared against; each switch at 0 keeps selecting exactly the path it
+    selected before the later kernels existed.)"""
+    L = lib()
+    return all(L.msmp_tune_query(k) for k in keys + (b'wide_msg', b'split', b'lem_wide'))
 
 
 DENSE_MESSAGE = False     # True: evaluate message_net_1 on the per-edge concatenation (reference order of operations)
@@ -279,9 +274,7 @@ def _wide_head_aggregate(h, feat_cat, k_feat, gs, layer, ld, ws):
     _wide_linear(feat_cat, k_feat, wq, None, W, 0, Q, ws)
     agg = torch.empty(n, ld, dtype=torch.float32, device=dev)
     fused = False
-    # (msmp_tune("lem_wide", 0) selects the unfused width-generic path as a WHOLE: the model is then independent of "split", bitwise the
-    # exact-fp32 evaluation, which is what that setting is compared against)
-    if L.msmp_tune_query(b'wide_msg') and L.msmp_tune_query(b'split') and L.msmp_tune_query(b'lem_wide'):
+    if _wide_fused():
         # the message half as ONE launch, nothing edge-sized in memory (wide_message_kernel.hip); an in-degree above the kernel's cap
         # (msmp_wide_message_max_in_degree) is refused by value and takes the three launches below, like msmp_edge_aggregate_f32 above 256
         blob = layer.wide_message_blob()
@@ -338,10 +331,9 @@ def _mp_layer_wide(h, u, pos_x, variables, gs, main, gate, eps):
     heads = [main] if gate is None else [main, gate]
     aggs = [_wide_head_aggregate(hp, feat_cat, k_feat, gs, layer, ld, ws) for layer in heads]
     out = torch.empty(n, ld, dtype=torch.float32, device=h.device)
-    # the node half of the layer as ONE launch (wide_node_tail_kernel.hip) while every switch of the fused width-generic path is on: each
-    # of "wide_msg", "split" and "lem_wide" at 0 keeps selecting exactly the path it selected before that kernel existed.  A graph above
-    # the kernel's cap (msmp_wide_node_tail_max_graph_nodes) is refused by value and takes the GEMMs below, like msmp_node_tail_f32 above 128
-    if (all(L.msmp_tune_query(k) for k in (b'wide_tail', b'wide_msg', b'split', b'lem_wide'))
+    # the node half of the layer as ONE launch (wide_node_tail_kernel.hip).  A graph above the kernel's cap
+    # (msmp_wide_node_tail_max_graph_nodes) is refused by value and takes the GEMMs below, like msmp_node_tail_f32 above 128
+    if (_wide_fused(b'wide_tail')
             and gs.max_graph_nodes <= L.msmp_wide_node_tail_max_graph_nodes(min(W, 256))):
         blobs = [layer.wide_tail_blob() for layer in heads]
         if all(b is not None for b in blobs):

@@ -14,7 +14,7 @@ import math
 import torch
 from torch import nn
 
-from ._lib import lib, check, ptr, current_stream, MSMP_ERR_UNSUPPORTED, PARAM_EPOCH
+from ._lib import lib, check, ptr, current_stream, MSMP_ERR_UNSUPPORTED, PackedCache
 
 
 class LEMcuda(nn.Module):
@@ -27,15 +27,14 @@ class LEMcuda(nn.Module):
         self.weights_lin_z = nn.Parameter(torch.empty(nhid, ninp + nhid, dtype=torch.float32))
         self.bias = nn.Parameter(torch.empty(3 * nhid, dtype=torch.float32))
         self.bias_lin_z = nn.Parameter(torch.empty(nhid, dtype=torch.float32))
-        self._wide_blob = None
-        self._wide_key = None
+        self._wide_blob = PackedCache()
         self.reset_parameters()
 
     def _pack_wide(self):
-        """The blob of msmp_lem_encoder_wide_f32, cached like LEM._pack: parameter addresses, versions and PARAM_EPOCH."""
+        """The blob of msmp_lem_encoder_wide_f32, cached like LEM._pack (PackedCache)."""
         ps = [self.weights, self.weights_lin_z, self.bias, self.bias_lin_z]
-        key = (PARAM_EPOCH[0],) + tuple((p.data_ptr(), p._version, str(p.device)) for p in ps)
-        if key != self._wide_key:
+
+        def build():
             L = lib()
             n_floats = L.msmp_packed_lem_wide_floats(self.ninp, self.nhid)
             if n_floats <= 0:
@@ -43,8 +42,8 @@ class LEMcuda(nn.Module):
             blob = torch.empty(n_floats, dtype=torch.float32, device=ps[0].device)
             f = [p.detach().to(torch.float32).contiguous() for p in ps]
             check(L.msmp_pack_lem_wide_f32(*[ptr(t) for t in f], self.ninp, self.nhid, ptr(blob), current_stream()), 'msmp_pack_lem_wide_f32')
-            self._wide_blob, self._wide_key = blob, key
-        return self._wide_blob
+            return blob
+        return self._wide_blob.get(ps, build)
 
     def wide_kernel_selected(self):
         """True where a no-grad fp32 CUDA forward is ONE msmp_lem_encoder_wide_f32 launch: msmp_tune "lem_wide" and "split" both on
@@ -182,8 +181,7 @@ class LEM(nn.Module):
         super().__init__()
         self.ninp, self.nhid = ninp, nhid
         self.rnn = LEMcuda(ninp, nhid, dt)
-        self._packed = None
-        self._packed_key = None
+        self._packed = PackedCache()
 
     def forward(self, inputs):
         """inputs [T, N, ninp] (the reference's layout) -> all_y[-1] [N, nhid]."""
@@ -206,15 +204,15 @@ class LEM(nn.Module):
         ps = [self.rnn.weights, self.rnn.weights_lin_z, self.rnn.bias, self.rnn.bias_lin_z]
         if mlp is not None:
             ps += [mlp[0].weight, mlp[0].bias, mlp[2].weight, mlp[2].bias]
-        key = (PARAM_EPOCH[0],) + tuple((p.data_ptr(), p._version, str(p.device)) for p in ps)
-        if key != self._packed_key:
+
+        def build():
             L = lib()
             blob = torch.empty(L.msmp_packed_lem_floats(), dtype=torch.float32, device=ps[0].device)
             f = [p.detach().to(torch.float32).contiguous() for p in ps]
             args = [ptr(t) for t in f] + [None] * (8 - len(f))
             check(L.msmp_pack_lem_f32(*args, self.ninp, ptr(blob), current_stream()), 'msmp_pack_lem_f32')
-            self._packed, self._packed_key = blob, key
-        return self._packed
+            return blob
+        return self._packed.get(ps, build)
 
     def encode_nodes(self, u, pos_x, pos_t, variables, dt_cum, two_d, mlp=None):
         """Same as `encode` with the step inputs assembled inside the kernel from the node arrays (models_gnn.py:1357-1360 /

@@ -23,7 +23,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from ._lib import lib, check, ptr, current_stream, PARAM_EPOCH
+from ._lib import lib, check, ptr, current_stream, PARAM_EPOCH, PackedCache, cached_operands
 from .graph import structure_of
 from .layers import GNN_Layer, GNN_LayerLin, Swish, mp_layer, node_features
 from .lem import LEM, LEMS
@@ -316,14 +316,16 @@ class _SolverBase(nn.Module):
         """Packed embedding_mlp weights (msmp_pack_mlp2_f32), cached per parameter version; built on the CURRENT stream."""
         lin1, lin2 = self.embedding_mlp[0], self.embedding_mlp[2]
         ps = (lin1.weight, lin1.bias, lin2.weight, lin2.bias)
-        key = (PARAM_EPOCH[0],) + tuple((p.data_ptr(), p._version, str(p.device)) for p in ps)
-        if getattr(self, '_embed_key', None) != key:
+
+        def build():
             L = lib()
             f = [p.detach().to(torch.float32).contiguous() for p in ps]
             blob = torch.empty(L.msmp_packed_mlp2_floats(lin1.in_features), dtype=torch.float32, device=dev)
             check(L.msmp_pack_mlp2_f32(*[ptr(t) for t in f], lin1.in_features, ptr(blob), current_stream()), 'msmp_pack_mlp2_f32')
-            self._embed_blob, self._embed_key = blob, key
-        return self._embed_blob
+            return blob
+        if getattr(self, '_embed_blob', None) is None:
+            self._embed_blob = PackedCache()
+        return self._embed_blob.get(ps, build)
 
     def _embed_hip(self, u, pos_x, variables):
         """embedding_mlp as one HIP kernel (msmp_mlp2_swish_f32); the packed weights are cached per parameter version."""
@@ -598,7 +600,7 @@ class _GraphedForward:
     * the static input buffers (x, pos) and the output;
     * a PRIVATE layer workspace (layers._Workspace.private): the shared grow-only workspace of the eager path is replaced, and
       its old buffer freed, as soon as any later call needs a larger one;
-    * the packed weight blobs the capture read (`layer._packed`, the encoder blobs): they are replaced after an optimizer step,
+    * the packed weight blobs the capture read (every PackedCache of the model's modules): they are replaced after an optimizer step,
       load_state_dict or invalidate_packed_weights().  References keep their memory alive, and `__call__` compares what the
       blobs' caches key on (optimizer epoch, parameter storages and versions) with the capture-time values: on a mismatch the
       graph is re-captured, never replayed against stale weights."""
@@ -620,7 +622,7 @@ class _GraphedForward:
                 (float(pde.dt), float(pde.L), float(pde.tmax)))
 
     def _weight_blobs(self):
-        return [getattr(m, attr) for m in self.model.modules() for attr in ('_packed', '_embed_blob') if getattr(m, attr, None) is not None]
+        return cached_operands(self.model)
 
     @torch.no_grad()          # a re-capture from __call__ may come from a training loop: never capture the autograd path
     def _capture(self):

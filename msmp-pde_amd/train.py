@@ -107,7 +107,7 @@ class CapturedTrainStep:
         import copy
         from . import autograd as _ag
         from .layers import _Workspace
-        from ._lib import invalidate_packed_weights
+        from ._lib import invalidate_packed_weights, cached_operands
         if not all(g.get('capturable') for g in optimizer.param_groups):
             raise RuntimeError('CapturedTrainStep needs msmp_pde_amd.optim.AdamW(..., capturable=True)')
         self.model, self.opt = model, optimizer
@@ -181,7 +181,7 @@ class CapturedTrainStep:
         finally:
             if old_bwd is not None:
                 _ag._bwd_ws[dev] = old_bwd
-        self._blobs = [getattr(m, a) for m in model.modules() for a in ('_packed', '_embed_blob') if getattr(m, a, None) is not None]
+        self._blobs = cached_operands(model)
         self._params = [(p, p.data_ptr()) for p in params]
         # the optimizer-side memory the graph points at: moments, device step count and learning rate (optimizer.load_state_dict
         # replaces the group dicts and the state tensors; a replay would then read and write freed memory)
