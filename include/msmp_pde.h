@@ -99,12 +99,16 @@ int msmp_last_status(int* flags_out, int reset);
  *             pair) as one msmp_wide_node_tail_f32 launch on graphs of up to 128 nodes; 0 (default): per head a concatenation and two
  *             msmp_linear_f32, then msmp_wide_norm_blend_f32 (the entry itself does not read the key).  The host takes the fused launch only while "wide_msg",
  *             "split" and "lem_wide" are 1 as well, so each of those keeps selecting the path it selected before this kernel.
+ *   "wide_proj" 1: the host's no-grad layer at widths other than 128 evaluates the P / Q projections of message_net_1 (both heads of
+ *             a gated pair) as one msmp_wide_node_proj_f32 launch; 0 (default): a concatenation [h | u | pos | vars] and two msmp_linear_f32 per head
+ *             (the entry itself does not read the key).  The host takes the fused launch only while "wide_msg", "split" and "lem_wide" are 1
+ *             as well, so each of those keeps selecting the path it selected before this kernel.
  *   "tile_arith" 1 (default): ranged tiles take their node rows by arithmetic on tile_halo; 0: always through the node list.
  *   "tail"    1 (default): msmp_mp_layer_f32 uses msmp_node_tail_f32 for graphs of up to 128 nodes; 0: the piecewise kernels.
  *   "pair"    gated pair: both heads' projection / message kernels in one launch each (bit-identical results): 0 never,
  *             1 (default) for batches of up to 65 536 nodes, where a step is bound by the latency of its ~60 dependent launches, 2 always. */
 int msmp_tune(const char* key, int value);
-int msmp_tune_query(const char* key);      /* current value of "split", "tail", "pair", "bwd_gemm", "tile", "tile_arith", "lem_wide", "wide_msg", "wide_tail", ... (0 for unknown keys) */
+int msmp_tune_query(const char* key);      /* current value of "split", "tail", "pair", "bwd_gemm", "tile", "tile_arith", "lem_wide", "wide_msg", "wide_tail", "wide_proj", ... (0 for unknown keys) */
 
 /* ---------------------------------------------------------------------------------------------
  * Weights
@@ -589,6 +593,28 @@ int msmp_wide_node_tail_max_graph_nodes(int width);
 int msmp_wide_node_tail_f32(const float* h, const float* agg_main, const float* agg_gate, const float* vars, const int32_t* graph_ptr,
                             int64_t n_nodes, int64_t n_graphs, int max_graph_nodes, int nv, int width, int ld, const float* packed_main,
                             const float* packed_gate, float eps, float* out, msmp_stream_t stream);
+/* The per-node projections of the factorised message_net_1 at any hidden width 1 <= width <= 256 in ONE launch, both heads of a gated pair;
+ * the concatenated rows [h | u | pos | vars] do not go to memory (experiments/models_gnn.py:132-138):
+ *   P[n] = w1[:, 0:W] h_n + w1[:, 2W:] [u_n | pos_n | vars_n] + b1          Q[n] = w1[:, W:2W] h_n - w1[:, 2W:2W+tw+1] [u_n | pos_n]
+ * so that message_net_1 of the edge j -> i is Swish(P[i] + Q[j]) (msmp_wide_message_f32 takes P and Q).  A node's rows depend on nothing
+ * but that node's inputs and the weights: not on the nodes around it, on n_nodes, or on the run (bitwise).  fp16-split MFMA arithmetic of
+ * the default path with node rows scaled by 2^8: an h or feature element with |x| > 255 or not finite raises MSMP_STATUS_NODE_SATURATED.
+ * Blob size / pack (experiments/models_gnn.py:132-138: message_net_1[0].weight [width, 2 width + tw + 1 + nv] and .bias, as in the
+ * state_dict): scales [8] | b1 [Wp] | the fp16 hi / lo fragments of the P and Q matrices times 2^s (Q's tail: the negated u | pos columns,
+ * zeros for the variables), zero-filled up to Wp = 32 KT, KT = ceil(width / 32), and up to TS = ceil((tw + 1 + nv) / 16) K = 16 steps of
+ * the tail: 8 + 32 KT + 1024 KT (2 KT + TS) floats; the power of two is chosen on the device.  0 and msmp_last_error for a width outside
+ * 1..256, tw < 1, nv outside 1..8 or tw + 1 + nv > 128. */
+int64_t msmp_packed_wide_proj_floats(int width, int tw, int nv);
+/* experiments/models_gnn.py:132-138 (message_net_1[0] of GNN_LayerLin).  MSMP_ERR_ARG outside the ranges above or for a null pointer. */
+int msmp_pack_wide_proj_f32(const float* w1, const float* b1, int width, int tw, int nv, float* packed_out, msmp_stream_t stream);
+/* experiments/models_gnn.py:132-138.  h, p_*, q_* [n_nodes, ld] with ld a multiple of 4 in width .. 4096, 16-byte aligned (columns
+ * width .. ld - 1 of h are not used, of the outputs they are written as 0; nothing outside the outputs is written); feat: the rows of
+ * msmp_pack_node_features_f32 at stride msmp_node_feature_stride(tw, nv), 16-byte aligned.  packed_gate == p_gate == q_gate == NULL selects
+ * the form with one head; a partial set of the three is MSMP_ERR_ARG.  MSMP_ERR_UNSUPPORTED for a width outside 1..256 or
+ * tw + 1 + nv > 128 (the caller keeps the row GEMMs); MSMP_ERR_ARG for a null or misaligned pointer, a bad ld, tw < 1, nv outside 1..8 or
+ * negative sizes; n_nodes == 0 is a no-op.  Allocates nothing and never synchronises. */
+int msmp_wide_node_proj_f32(const float* h, const float* feat, int64_t n_nodes, int tw, int nv, int width, int ld, const float* packed_main,
+                            const float* packed_gate, float* p_main, float* q_main, float* p_gate, float* q_gate, msmp_stream_t stream);
 /* gate_pre == NULL: out = InstanceNorm(main_pre); else out = (1 - tau) h + tau Swish(IN(main_pre)), tau = sigmoid(IN(gate_pre)) */
 int msmp_wide_norm_blend_f32(const float* h, const float* gate_pre, const float* main_pre, const int32_t* graph_ptr, int64_t n_graphs,
                              int width, int ld, float eps, float* out, msmp_stream_t stream);

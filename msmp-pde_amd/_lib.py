@@ -116,6 +116,9 @@ SIGNATURES = {
     'msmp_pack_wide_tail_f32': (c_int, [c_void_p] * 4 + [c_int, c_int, c_void_p, c_void_p]),
     'msmp_wide_node_tail_max_graph_nodes': (c_int, [c_int]),
     'msmp_wide_node_tail_f32': (c_int, [c_void_p] * 5 + [c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
+    'msmp_packed_wide_proj_floats': (c_int64, [c_int, c_int, c_int]),
+    'msmp_pack_wide_proj_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'msmp_wide_node_proj_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int] + [c_void_p] * 7),
     'msmp_wide_norm_blend_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_void_p, c_void_p]),
     'msmp_timing_enable': (c_int, [c_int]),
     'msmp_timing_reset': (c_int, []),

@@ -25,6 +25,7 @@ SOURCES = {  # file -> extra flags
     'lem_wide_kernel.hip': [],
     'wide_message_kernel.hip': [],
     'wide_node_tail_kernel.hip': [],
+    'wide_node_proj_kernel.hip': [],
     'train_kernels.hip': [],
     'mlp2_kernel.hip': [],
     'wide_kernels.hip': [],

@@ -1428,6 +1428,7 @@ extern int g_lem_share;
 extern int g_lem_wide;
 extern int g_wide_msg;
 extern int g_wide_tail;
+extern int g_wide_proj;
 // the sticky range status is the fp16-split path's: the exact-fp32 kernels have no range to leave (they run the data the split path could not)
 static int* split_status() { return msmp_tune_get("split") ? msmp::status_ptr() : nullptr; }
 static int g_split = 1;      // fp16-split matrix path (default); msmp_tune("split", 0) selects the fp32-MFMA kernels
@@ -1495,6 +1496,7 @@ int msmp_tune_get(const char* key) {
     if (!strcmp(key, "lem_wide")) return g_lem_wide;
     if (!strcmp(key, "wide_msg")) return g_wide_msg;
     if (!strcmp(key, "wide_tail")) return g_wide_tail;
+    if (!strcmp(key, "wide_proj")) return g_wide_proj;
     return 0;
 }
 
@@ -1514,6 +1516,7 @@ extern "C" int msmp_tune(const char* key, int value) {
     if (key && !strcmp(key, "lem_wide")) { g_lem_wide = value != 0; return MSMP_OK; }
     if (key && !strcmp(key, "wide_msg")) { g_wide_msg = value != 0; return MSMP_OK; }
     if (key && !strcmp(key, "wide_tail")) { g_wide_tail = value != 0; return MSMP_OK; }
+    if (key && !strcmp(key, "wide_proj")) { g_wide_proj = value != 0; return MSMP_OK; }
     if (key && !strcmp(key, "edge_nb")) { g_edge_nb = value; return MSMP_OK; }
     if (key && !strcmp(key, "split")) { g_split = value; return MSMP_OK; }
     msmp::set_error("msmp_tune: unknown key");

@@ -93,7 +93,7 @@ class _MPLayerBase(nn.Module):
         self.message_net_2 = nn.Sequential(_linear(hidden_features, hidden_features), Swish())
         self.update_net_1 = nn.Sequential(_linear(in_features + hidden_features + n_variables, hidden_features), Swish())
         self._make_update_net_2(hidden_features, out_features)
-        self._packed, self._wide_w, self._wide_msg, self._wide_tail = (_lib.PackedCache() for _ in range(4))
+        self._packed, self._wide_w, self._wide_msg, self._wide_tail, self._wide_proj = (_lib.PackedCache() for _ in range(5))
         self._ps = None
 
     def _params8(self):
@@ -149,6 +149,24 @@ class _MPLayerBase(nn.Module):
             check(L.msmp_pack_wide_msg_f32(ptr(f[0]), ptr(f[1]), W, ptr(blob), current_stream()), 'msmp_pack_wide_msg_f32')
             return blob
         return self._wide_msg.get((w2, b2), build)
+
+    def wide_proj_blob(self):
+        """message_net_1 in the layout of the fused wide projection kernel (msmp_pack_wide_proj_f32: fp16 hi / lo fragments of the P and Q
+        matrices times 2^s, scaled bias; the kernel splits W1 itself, wide_weights() is not needed on that path), cached per parameter
+        version like wide_message_blob(); None where the kernel does not exist (hidden width above 256, more than 128 feature columns)."""
+        L = lib()
+        W, tw, nv = self.hidden_features, self.time_window, self.n_variables
+        n_floats = L.msmp_packed_wide_proj_floats(W, tw, nv)
+        if n_floats <= 0:
+            return None
+        w1, b1 = self._params8()[0:2]
+
+        def build():
+            blob = torch.empty(n_floats, dtype=torch.float32, device=w1.device)
+            f = [_f32c(w1), _f32c(b1)]
+            check(L.msmp_pack_wide_proj_f32(ptr(f[0]), ptr(f[1]), W, tw, nv, ptr(blob), current_stream()), 'msmp_pack_wide_proj_f32')
+            return blob
+        return self._wide_proj.get((w1, b1), build)
 
     def wide_tail_blob(self):
         """update_net_1 / update_net_2 in the layout of the fused wide node tail (msmp_pack_wide_tail_f32: fp16 hi / lo fragments of W3 2^s3 and
@@ -262,16 +280,45 @@ def _wide_linear(x, k, w, bias, n_out, mode, out, ws):
                             ptr(ws), ws.numel(), current_stream()), 'msmp_linear_f32')
 
 
-def _wide_head_aggregate(h, feat_cat, k_feat, gs, layer, ld, ws):
-    """The message half of one GNN_LayerLin head at hidden width W != 128: the mean aggregate [N, ld] (experiments/models_gnn.py:132-138, :107)."""
+def _wide_projections(hp, h, u, pos_x, variables, feat, heads, ld, ws):
+    """P and Q [N, ld] of every head: the per-node projections of the factorised message_net_1 (experiments/models_gnn.py:132-138)."""
     L = lib()
-    n, W, e = h.shape[0], layer.hidden_features, gs.n_edges
-    wp, wq, b1, w2, b2, w3, b3, w4, b4 = layer.wide_weights()
-    dev = h.device
-    P = torch.empty(n, ld, dtype=torch.float32, device=dev)
-    Q = torch.empty(n, ld, dtype=torch.float32, device=dev)
-    _wide_linear(feat_cat, k_feat, wp, b1, W, 0, P, ws)
-    _wide_linear(feat_cat, k_feat, wq, None, W, 0, Q, ws)
+    n, dev = hp.shape[0], hp.device
+    W, tw, nv = heads[0].hidden_features, u.shape[1], variables.shape[1]
+    PQ = [(torch.empty(n, ld, dtype=torch.float32, device=dev), torch.empty(n, ld, dtype=torch.float32, device=dev)) for _ in heads]
+    # all of them as ONE launch, nothing concatenated in memory (wide_node_proj_kernel.hip); more feature columns than the kernel takes are
+    # refused by value and take the row GEMMs below
+    if _wide_fused(b'wide_proj') and heads[0].time_window == tw and heads[0].n_variables == nv:
+        blobs = [layer.wide_proj_blob() for layer in heads]
+        if all(b is not None for b in blobs):
+            if feat is None:
+                feat = node_features(u, pos_x, variables)
+            gated = len(heads) == 2
+            rc = L.msmp_wide_node_proj_f32(ptr(hp), ptr(feat), n, tw, nv, W, ld, ptr(blobs[0]), ptr(blobs[1]) if gated else None, ptr(PQ[0][0]),
+                                           ptr(PQ[0][1]), ptr(PQ[1][0]) if gated else None, ptr(PQ[1][1]) if gated else None, current_stream())
+            if rc != _lib.MSMP_ERR_UNSUPPORTED:
+                check(rc, 'msmp_wide_node_proj_f32')
+                return PQ
+    feat_cat = torch.cat((h, u, pos_x.reshape(-1, 1), variables), 1)
+    k_feat = feat_cat.shape[1]
+    pad = (-feat_cat.shape[1]) % 4
+    if pad:
+        feat_cat = torch.nn.functional.pad(feat_cat, (0, pad))
+    feat_cat = feat_cat.contiguous()
+    for layer, (P, Q) in zip(heads, PQ):
+        wp, wq, b1 = layer.wide_weights()[:3]
+        _wide_linear(feat_cat, k_feat, wp, b1, W, 0, P, ws)
+        _wide_linear(feat_cat, k_feat, wq, None, W, 0, Q, ws)
+    return PQ
+
+
+def _wide_head_aggregate(P, Q, gs, layer, ld, ws):
+    """The message half of one GNN_LayerLin head at hidden width W != 128 from its projections P, Q [N, ld]: the mean aggregate [N, ld]
+    (experiments/models_gnn.py:132-138, :107)."""
+    L = lib()
+    n, W, e = P.shape[0], layer.hidden_features, gs.n_edges
+    w2, b2 = layer.wide_weights()[3:5]
+    dev = P.device
     agg = torch.empty(n, ld, dtype=torch.float32, device=dev)
     fused = False
     if _wide_fused():
@@ -310,8 +357,9 @@ def _wide_head_update(h, agg, variables, layer, ld, ws):
     return y
 
 
-def _mp_layer_wide(h, u, pos_x, variables, gs, main, gate, eps):
-    """GNN_LayerLin (or a gated pair of them) at a hidden width other than 128: the HIP path of wide_kernels.hip.  h [N, W]."""
+def _mp_layer_wide(h, u, pos_x, variables, gs, main, gate, eps, feat=None):
+    """GNN_LayerLin (or a gated pair of them) at a hidden width other than 128: the HIP path of wide_kernels.hip.  h [N, W].
+    feat: the rows of node_features(u, pos_x, variables) where the caller has them (the solvers: once per forward)."""
     L = lib()
     W = main.hidden_features
     if main.MODE != _lib.MSMP_LAYER_LIN:
@@ -320,16 +368,11 @@ def _mp_layer_wide(h, u, pos_x, variables, gs, main, gate, eps):
     n = h.shape[0]
     hp = torch.zeros(n, ld, dtype=torch.float32, device=h.device)
     hp[:, :W] = h
-    feat_cat = torch.cat((h, u, pos_x.reshape(-1, 1), variables), 1)
-    k_feat = feat_cat.shape[1]
-    pad = (-feat_cat.shape[1]) % 4
-    if pad:
-        feat_cat = torch.nn.functional.pad(feat_cat, (0, pad))
-    feat_cat = feat_cat.contiguous()
-    k_max = max(feat_cat.shape[1], 2 * W + variables.shape[1] + 3)
+    k_max = max(W + u.shape[1] + 1 + variables.shape[1] + 3, 2 * W + variables.shape[1] + 3)
     ws = _Workspace.get(L.msmp_linear_workspace_bytes(k_max, W), h.device)
     heads = [main] if gate is None else [main, gate]
-    aggs = [_wide_head_aggregate(hp, feat_cat, k_feat, gs, layer, ld, ws) for layer in heads]
+    PQ = _wide_projections(hp, h, u, pos_x, variables, feat, heads, ld, ws)
+    aggs = [_wide_head_aggregate(P, Q, gs, layer, ld, ws) for layer, (P, Q) in zip(heads, PQ)]
     out = torch.empty(n, ld, dtype=torch.float32, device=h.device)
     # the node half of the layer as ONE launch (wide_node_tail_kernel.hip).  A graph above the kernel's cap
     # (msmp_wide_node_tail_max_graph_nodes) is refused by value and takes the GEMMs below, like msmp_node_tail_f32 above 128
@@ -391,7 +434,7 @@ def mp_layer(h, u, pos_x, variables, structure, main, gate=None, eps=1e-5, dense
     if main.wide:
         if need_grad:
             return _mp_layer_wide_autograd(h, u.to(h.dtype), pos_x, variables.to(h.dtype), gs, main, gate, eps)
-        return _mp_layer_wide(_f32c(h), _f32c(u), _f32c(pos_x).reshape(-1), _f32c(variables), gs, main, gate, eps)
+        return _mp_layer_wide(_f32c(h), _f32c(u), _f32c(pos_x).reshape(-1), _f32c(variables), gs, main, gate, eps, feat)
     hd, u, pos_x, variables = _f32c(h), _f32c(u), _f32c(pos_x).reshape(-1), _f32c(variables)
     n = hd.shape[0]
     assert n == gs.n_nodes and hd.shape[1] == HIDDEN and u.shape[1] == main.time_window

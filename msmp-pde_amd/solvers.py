@@ -25,7 +25,7 @@ from torch import nn
 from . import _lib
 from ._lib import lib, check, ptr, current_stream, PARAM_EPOCH, PackedCache, cached_operands
 from .graph import structure_of
-from .layers import GNN_Layer, GNN_LayerLin, Swish, mp_layer, node_features
+from .layers import GNN_Layer, GNN_LayerLin, Swish, mp_layer, node_features, _wide_fused
 from .lem import LEM, LEMS
 from .reductions import bias_add
 
@@ -512,7 +512,11 @@ class _SolverBase(nn.Module):
         gs = structure_of(data)
         tw = self.time_window
         # the [u | pos | vars] columns of message_net_1's input do not change over the layers: packed once for the tile kernel
-        want_feat = not torch.is_grad_enabled() and self.hidden_features == 128 and gs.tiles() is not None
+        # ... and for the fused projections of the width-generic layers (msmp_wide_node_proj_f32)
+        if self.hidden_features == 128:
+            want_feat = not torch.is_grad_enabled() and gs.tiles() is not None
+        else:
+            want_feat = not torch.is_grad_enabled() and u_in.is_cuda and _wide_fused(b'wide_proj')
         prep = self._prepare(data, want_feat) if u_in.is_cuda else None
         if prep is not None:            # one HIP launch
             u, pos_x, pos_t, variables, feat = prep
