@@ -2,7 +2,10 @@
 missing or a call fails, this raises."""
 import ctypes
 import os
+import threading
 from ctypes import c_int, c_int64, c_size_t, c_void_p, c_float, c_double, c_char_p
+
+import torch
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('MSMP_LIB_PATH') or os.path.join(PKG, 'libmsmp_pde.so')     # MSMP_LIB_PATH: a diagnostic build of the same library
@@ -220,12 +223,70 @@ def current_stream():
     Goes through the C accessor: building a torch.cuda.Stream object per kernel launch costs ~10 us of host time, which is
     what bounds small batches (the launches of a 32-graph rollout step, the backward of a 16-graph training batch)."""
     global _raw_stream
-    import torch
     if _raw_stream is None:
         _raw_stream = getattr(torch._C, '_cuda_getCurrentRawStream', False)
     if _raw_stream:
         return _raw_stream(torch.cuda.current_device())
     return torch.cuda.current_stream().cuda_stream
+
+
+def _f32c(t):
+    return t.detach().to(torch.float32).contiguous()
+
+
+def node_features(u, pos_x, variables):
+    """[u | pos | vars | 0-pad] rows of msmp_pack_node_features_f32: the columns of message_net_1's input that are the same for
+    every layer of a forward.  Packed once per forward by the solvers and handed to every layer call (`feat`)."""
+    L = lib()
+    n, tw, nv = u.shape[0], u.shape[1], variables.shape[1]
+    stride = L.msmp_node_feature_stride(tw, nv)
+    feat = torch.empty(n, stride, dtype=torch.float32, device=u.device)
+    check(L.msmp_pack_node_features_f32(ptr(u), ptr(pos_x), ptr(variables), n, tw, nv, ptr(feat), current_stream()),
+          'msmp_pack_node_features_f32')
+    return feat
+
+
+class _Workspace(object):
+    """Grow-only scratch buffer per (device, stream), shared by all layers (the C-ABI never allocates; forwards issued on different
+    streams of one device must not share scratch memory).  `private(device)` is a context
+    in which the layers of the calling thread use buffers of their own instead (hipGraph capture: the captured launches must
+    point at memory nobody replaces; solvers._GraphedForward keeps those buffers alive as long as the graph)."""
+    _bufs = {}
+    _tls = threading.local()      # `.private`: the calling THREAD's private buffer (a capture on one thread must not redirect another thread's forward)
+
+    class _Private(object):
+        def __init__(self, device):
+            self.device, self.buf = device, None
+
+        def __enter__(self):
+            self._outer = getattr(_Workspace._tls, 'private', None)
+            _Workspace._tls.private = self
+            return self
+
+        def __exit__(self, *exc):
+            _Workspace._tls.private = self._outer
+
+        def buffers(self):
+            return [self.buf]
+
+    @classmethod
+    def private(cls, device):
+        return cls._Private(device)
+
+    @classmethod
+    def get(cls, nbytes, device):
+        p = getattr(cls._tls, 'private', None)
+        if p is not None and p.device == device:
+            if p.buf is None or p.buf.numel() < nbytes:
+                assert not torch.cuda.is_current_stream_capturing() or p.buf is None, 'workspace grew during capture'
+                p.buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+            return p.buf
+        key = (device, torch.cuda.current_stream(device).cuda_stream)
+        buf = cls._bufs.get(key)
+        if buf is None or buf.numel() < nbytes:
+            buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+            cls._bufs[key] = buf
+        return buf
 
 
 def timing_read(kernel):

@@ -45,11 +45,15 @@ class LEMcuda(nn.Module):
             return blob
         return self._wide_blob.get(ps, build)
 
+    def wide_kernel_exists(self):
+        """True at the sizes msmp_lem_encoder_wide_f32 takes."""
+        return 1 <= self.ninp <= 8 and 1 <= self.nhid <= 256
+
     def wide_kernel_selected(self):
         """True where a no-grad fp32 CUDA forward is ONE msmp_lem_encoder_wide_f32 launch: msmp_tune "lem_wide" and "split" both on
         (the exact-fp32 path, `_lib.exact_fp32()`, keeps the GEMM + pointwise loop: Solver.range_policy falls back to it)."""
         L = lib()
-        return bool(L.msmp_tune_query(b'lem_wide')) and bool(L.msmp_tune_query(b'split')) and 1 <= self.ninp <= 8 and 1 <= self.nhid <= 256
+        return bool(L.msmp_tune_query(b'lem_wide')) and bool(L.msmp_tune_query(b'split')) and self.wide_kernel_exists()
 
     def forward_wide(self, xin, states=None):
         """xin [N, T, ninp] node-major fp32 CUDA, states (y0, z0) or None -> (y_T, z_T) on the width-generic HIP recurrence kernel."""

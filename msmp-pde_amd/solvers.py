@@ -23,11 +23,12 @@ import torch
 from torch import nn
 
 from . import _lib
-from ._lib import lib, check, ptr, current_stream, PARAM_EPOCH, PackedCache, cached_operands
+from ._lib import lib, check, ptr, current_stream, PARAM_EPOCH, PackedCache, cached_operands, node_features, _Workspace
 from .graph import structure_of
-from .layers import GNN_Layer, GNN_LayerLin, Swish, mp_layer, node_features, _wide_fused
+from .layers import GNN_Layer, GNN_LayerLin, Swish, mp_layer
 from .lem import LEM, LEMS
 from .reductions import bias_add
+from .wide import _wide_fused, lemoutput_mlp
 
 _DECODER = {20: (15, 4, 10), 25: (16, 3, 14), 50: (12, 2, 10)}   # models_gnn.py:210-224; models_gnn2D.py:79-88
 
@@ -263,7 +264,7 @@ class _SolverBase(nn.Module):
         if self.hidden_features != 128:     # the GLU classes (any width; lem.LEM.forward_nodes): no grad = the width-generic HIP recurrence + two HIP row GEMMs
             y = self.embedding_lem.forward_nodes(self._step_inputs(u, pos_x, pos_t, variables, dt))
             if not torch.is_grad_enabled() and y.dtype == torch.float32 and self.embedding_lem.rnn.wide_kernel_selected():
-                return self._lemoutput_mlp_hip(y)
+                return lemoutput_mlp(self.lemoutput_mlp, y)
             return self.lemoutput_mlp(y)
         grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.embedding_lem.parameters())
         if not grad:                    # step inputs assembled inside the kernel (no [N, T, ninp] tensor)
@@ -275,23 +276,6 @@ class _SolverBase(nn.Module):
             h = self.embedding_lem.forward_nodes(lem_in)       # HIP training kernels (recurrence forward + BPTT)
             return self.lemoutput_mlp(h)
         return self.embedding_lem.encode(lem_in, self.lemoutput_mlp)       # fused HIP kernel (recurrence + MLP)
-
-    def _lemoutput_mlp_hip(self, y):
-        """lemoutput_mlp (models_gnn.py:1287-1291: Linear + Swish + Linear + Swish) at a width other than 128 as two msmp_linear_f32
-        calls with the bias + Swish epilogue (mode 1)."""
-        from .layers import _wide_linear, _Workspace
-        W, n = self.hidden_features, y.shape[0]
-        ld = 128 * ((W + 127) // 128)
-        x = torch.nn.functional.pad(y, (0, (-W) % 4)).contiguous()
-        w = [p.detach().to(torch.float32).contiguous() for p in (self.lemoutput_mlp[0].weight, self.lemoutput_mlp[0].bias,
-                                                                   self.lemoutput_mlp[2].weight, self.lemoutput_mlp[2].bias)]
-        ws = _Workspace.get(lib().msmp_linear_workspace_bytes(W, W), y.device)
-        a = torch.empty(n, ld, dtype=torch.float32, device=y.device)
-        b = torch.empty(n, ld, dtype=torch.float32, device=y.device)
-        _wide_linear(x, W, w[0], w[1], W, 1, a, ws)
-        _wide_linear(a, W, w[2], w[3], W, 1, b, ws)
-        b._msmp_keep = w            # the kernels read the weights after this returns
-        return b[:, :W].contiguous()
 
     def _step_inputs(self, u, pos_x, pos_t, variables, dt):
         """The recurrent encoder's per-step inputs, node-major [N, T, ninp]."""
@@ -356,13 +340,12 @@ class _SolverBase(nn.Module):
         dev = dev or next(self.parameters()).device
         for layers in (self.gnn_layers, getattr(self, 'gnn_layers_gate', ())):
             for layer in layers:
-                if layer.wide:
-                    layer.wide_weights()
-                    layer.wide_message_blob()
-                else:
-                    layer.packed()
-        if self.LEM_ENCODER and not self.LSTM_ENCODER and self.hidden_features == 128 and not isinstance(self.embedding_lem, LEMS):
-            self.embedding_lem._pack(self.lemoutput_mlp)
+                layer.warm()
+        if self.LEM_ENCODER and not self.LSTM_ENCODER and not isinstance(self.embedding_lem, LEMS):
+            if self.hidden_features == 128:
+                self.embedding_lem._pack(self.lemoutput_mlp)
+            elif self.embedding_lem.rnn.wide_kernel_exists():       # whatever the switches say: a blob packed and not used costs microseconds
+                self.embedding_lem.rnn._pack_wide()
         elif not self.LEM_ENCODER and not self.LSTM_ENCODER:
             self._embed_packed(dev)
         self._dt(dev)
@@ -572,7 +555,6 @@ class _SolverBase(nn.Module):
                                          ptr(w[3]), float(self.pde.dt), ptr(out), current_stream()), 'msmp_decoder_f32')
         return out.to(u_in.dtype)
 
-
     def _double_mlp_hip(self, h):
         """double_mlp (models_gnn2D.py:66-70: Linear(128, 256) + Swish + Unflatten) as one HIP row GEMM with the bias and the Swish in its
         epilogue (msmp_linear_swish_f32); returns [N, 2, 128]."""
@@ -583,7 +565,6 @@ class _SolverBase(nn.Module):
         need = lib().msmp_linear_swish_workspace_bytes(k, n_out)
         if not need:
             raise RuntimeError(f'double_mlp of {k} -> {n_out} features is outside msmp_linear_swish_f32')
-        from .layers import _Workspace
         ws = _Workspace.get(need, h.device)         # per (device, stream); the layers are done with it by now
         out = torch.empty(h.shape[0], n_out, dtype=torch.float32, device=h.device)
         check(lib().msmp_linear_swish_f32(ptr(h), h.shape[0], k, ptr(w), ptr(b), n_out, ptr(out), ptr(ws), ws.numel(), current_stream()),
@@ -602,7 +583,7 @@ class _SolverBase(nn.Module):
 class _GraphedForward:
     """hipGraph of one forward.  The captured kernels hold RAW pointers, so everything they point at is owned or pinned here:
     * the static input buffers (x, pos) and the output;
-    * a PRIVATE layer workspace (layers._Workspace.private): the shared grow-only workspace of the eager path is replaced, and
+    * a PRIVATE layer workspace (_lib._Workspace.private): the shared grow-only workspace of the eager path is replaced, and
       its old buffer freed, as soon as any later call needs a larger one;
     * the packed weight blobs the capture read (every PackedCache of the model's modules): they are replaced after an optimizer step,
       load_state_dict or invalidate_packed_weights().  References keep their memory alive, and `__call__` compares what the
@@ -630,7 +611,6 @@ class _GraphedForward:
 
     @torch.no_grad()          # a re-capture from __call__ may come from a training loop: never capture the autograd path
     def _capture(self):
-        from .layers import _Workspace
         model = self.model
         self.graph = None
         with _Workspace.private(self.data.x.device) as ws:
@@ -704,7 +684,7 @@ class _GLUBase(_SolverBase):
     gated pair of CNNs on the two halves of the hidden state,  out = (1 - scale) u_last + cumsum(dt) scale diff  with
     scale = output_mlp_gate(h[..., :82]), diff = output_mlp_diff(h[..., 82:])  (experiments/models_gnn.py:1379-1523,
     models_gnn2D.py:1198-1366; no sigmoid on `scale`, as in the reference).  Layers: the width-generic HIP path
-    (layers._mp_layer_wide); without grad the LEM recurrence is one HIP launch (msmp_lem_encoder_wide_f32) and lemoutput_mlp two HIP row
+    (wide._mp_layer_wide); without grad the LEM recurrence is one HIP launch (msmp_lem_encoder_wide_f32) and lemoutput_mlp two HIP row
     GEMMs; double_mlp and the two small CNNs: PyTorch-ROCm ops."""
     GATED, LEM_ENCODER, LAYER = True, True, GNN_LayerLin
 

@@ -106,8 +106,7 @@ class CapturedTrainStep:
     def __init__(self, model, optimizer, graph, warmup=3):
         import copy
         from . import autograd as _ag
-        from .layers import _Workspace
-        from ._lib import invalidate_packed_weights, cached_operands
+        from ._lib import invalidate_packed_weights, cached_operands, _Workspace
         if not all(g.get('capturable') for g in optimizer.param_groups):
             raise RuntimeError('CapturedTrainStep needs msmp_pde_amd.optim.AdamW(..., capturable=True)')
         self.model, self.opt = model, optimizer

@@ -1,8 +1,10 @@
-"""Shared helpers for the tests: golden loading and synthetic E2-shaped batches (no reference needed)."""
+"""Shared helpers for the tests: golden loading, synthetic E2-shaped batches (no reference needed) and what the tests of the
+width-generic (hidden width != 128) path share."""
 import os
 from types import SimpleNamespace
 
 import numpy as np
+import pytest
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
@@ -215,3 +217,88 @@ def layer_error_profile(mp, kind, exp, bsz=8, seed=11, layers=6, tw=25):
     rec['out'] = {'hip': err_stats(out.double().cpu().numpy(), r64.out), 'f32': err_stats(r32.out, r64.out),
                   'ref_max': float(np.abs(r64.out).max())}
     return rec
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Shared by the GPU tests of the width-generic path (test_gpu_wide_*.py, test_gpu_lem_wide.py, the GLU cases of test_gpu_solver.py).
+# A test module that uses a fixture from here imports it by name.
+# ---------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope='module')
+def mp():
+    import torch
+    import msmp_pde_amd
+    assert torch.cuda.is_available()
+    msmp_pde_amd.lib()
+    return msmp_pde_amd
+
+
+WIDE_SWITCHES = (b'wide_msg', b'wide_tail', b'wide_proj', b'lem_wide', b'split')
+_SHIPPED_SWITCHES = {}
+
+
+@pytest.fixture
+def restore_wide_switches(mp):
+    """Every switch of the width-generic path is back at its shipped value (recorded at first use) after the test."""
+    L = mp.lib()
+    if not _SHIPPED_SWITCHES:
+        _SHIPPED_SWITCHES.update((key, L.msmp_tune_query(key)) for key in WIDE_SWITCHES)
+    yield
+    for key, value in _SHIPPED_SWITCHES.items():
+        L.msmp_tune(key, value)
+
+
+def ld_of(W):
+    """row stride of the [N, W] activations of the width-generic path"""
+    return 128 * ((W + 127) // 128)
+
+
+def ragged_edges(sizes=(1, 37, 100, 130, 5), seed=3):
+    """the graphs of test_wide_layer_pieces_vs_oracle: every seventh target without in-edges, in-degrees 1-5; (edge_index sorted by target,
+    batch, n)"""
+    rng = np.random.default_rng(seed)
+    starts = np.concatenate(([0], np.cumsum(sizes)))
+    src, dst = [], []
+    for g, sz in enumerate(sizes):
+        for t in range(sz):
+            if t % 7 == 3:
+                continue
+            for s_ in rng.choice(sz, size=min(sz, int(rng.integers(1, 6))), replace=False):
+                src.append(starts[g] + s_); dst.append(starts[g] + t)
+    order = np.argsort(np.array(dst), kind='stable')
+    ei = np.stack([np.array(src)[order], np.array(dst)[order]])
+    return ei, np.repeat(np.arange(len(sizes)), sizes), int(sum(sizes))
+
+
+def layer_inputs(n, W, tw, nv, seed):
+    """h standard normal [n, W], u standard normal [n, tw], pos [n, 1] and vars [n, nv] uniform in [0, 1): float32 on the GPU"""
+    import torch
+    rng = np.random.default_rng(seed)
+    h = torch.tensor(rng.standard_normal((n, W)), dtype=torch.float32).cuda()
+    u = torch.tensor(rng.standard_normal((n, tw)), dtype=torch.float32).cuda()
+    pos = torch.tensor(rng.uniform(0, 1, (n, 1)), dtype=torch.float32).cuda()
+    var = torch.tensor(rng.uniform(0, 1, (n, nv)), dtype=torch.float32).cuda()
+    return h, u, pos, var
+
+
+def oracle_layer(main, gate, args, ei, batch):
+    """the float64 oracle's GNN_LayerLin (or gated pair) on the fp32 inputs args = (h, u, pos, var)"""
+    from oracle import msmp_oracle as O
+    args64 = [t.double().cpu().numpy() for t in args]
+    sd = lambda m: {k: v.detach().double().cpu().numpy() for k, v in m.state_dict().items()}
+    ref = O.mp_layer(O.layer_params(sd(main), ''), *args64, ei, batch, lin=True)
+    if gate is None:
+        return ref
+    tau = O.sigmoid(O.mp_layer(O.layer_params(sd(gate), ''), *args64, ei, batch, lin=True))
+    return (1.0 - tau) * args64[0] + tau * O.swish(ref)
+
+
+def counted(mp, monkeypatch, name):
+    """the list that grows by one entry per call of the C-ABI entry `name` from here on (until monkeypatch undoes it)"""
+    L = mp.lib()
+    real, calls = getattr(L, name), []
+
+    def entry(*a):
+        calls.append(1)
+        return real(*a)
+    monkeypatch.setattr(L, name, entry)
+    return calls

@@ -617,9 +617,9 @@ def test_general_linear_kernel(mp, rows, k, n_out, mode):
 
 
 def test_wide_layer_pieces_vs_oracle(mp):
-    """The width-generic layer (hidden width 164; layers._mp_layer_wide = msmp_linear_f32 + wide_kernels.hip) against the float64
+    """The width-generic layer (hidden width 164; wide._mp_layer_wide = msmp_linear_f32 + wide_kernels.hip) against the float64
     oracle layer and against its PyTorch-ROCm autograd twin, gated and plain, on a ragged batch with zero in-degree nodes."""
-    from msmp_pde_amd.layers import _mp_layer_wide, _mp_layer_wide_autograd
+    from msmp_pde_amd.wide import _mp_layer_wide, _mp_layer_wide_autograd
     from msmp_pde_amd.graph import GraphStructure
     rng = np.random.default_rng(3)
     W, tw, nv = 164, 25, 2

@@ -11,27 +11,13 @@ import torch
 
 from oracle import msmp_oracle as O
 from helpers import synthetic_case
+from helpers import mp, restore_wide_switches       # noqa: F401  (fixtures)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('restore_wide_switches')]
 
 BAR = 5e-6
 WIDTHS = [33, 96, 128, 164, 192, 256]
 SHAPES = [(1, 1, 1), (5, 2, 33), (6, 25, 97), (8, 25, 300), (4, 50, 64)]       # (ninp, T, n)
-
-
-@pytest.fixture(scope='module')
-def mp():
-    import msmp_pde_amd
-    assert torch.cuda.is_available()
-    msmp_pde_amd.lib()
-    return msmp_pde_amd
-
-
-@pytest.fixture(autouse=True)
-def _restore_switches(mp):
-    yield
-    mp.lib().msmp_tune(b'split', 1)
-    mp.lib().msmp_tune(b'lem_wide', 1)
 
 
 def oracle_cell(rnn, xin, states=None):

@@ -2,51 +2,20 @@
 mean_j Swish(W2 Swish(P[i] + Q[j]) + b2) of GNN_LayerLin (experiments/models_gnn.py:132-138, :107) in one launch at any hidden width up to
 256, against the formula in numpy float64 from the same fp32 inputs; its bitwise properties (run to run, independent of the batch around a
 graph and of the tile cut), the padding columns, the in-degree cap and the fall-back above it, the range status, and the host paths that
-reach it: layers._mp_layer_wide and the two GLU solver classes.
+reach it: wide._mp_layer_wide and the two GLU solver classes.
 Bar 1e-6 max(1, max|ref|): the bar of test_layer_pieces_vs_oracle for the 128-wide message and aggregate kernels (same arithmetic)."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import msmp_oracle as O
-from helpers import synthetic_case
+from helpers import synthetic_case, ld_of, ragged_edges, layer_inputs, oracle_layer, counted
+from helpers import mp, restore_wide_switches       # noqa: F401  (fixtures)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('restore_wide_switches')]
 
 WIDTHS = [33, 96, 130, 164, 192, 256]          # KT 2, 3, 5, 6, 6, 8
 SIZES = [1, 37, 100, 130, 5]
-
-
-@pytest.fixture(scope='module')
-def mp():
-    import msmp_pde_amd
-    assert torch.cuda.is_available()
-    msmp_pde_amd.lib()
-    return msmp_pde_amd
-
-
-@pytest.fixture(autouse=True)
-def _restore_switches(mp):
-    yield
-    mp.lib().msmp_tune(b'wide_msg', 1)
-    mp.lib().msmp_tune(b'split', 1)
-    mp.lib().msmp_tune(b'lem_wide', 1)
-
-
-def ragged_edges():
-    """the batch of test_wide_layer_pieces_vs_oracle: sizes [1, 37, 100, 130, 5], every seventh target without in-edges, degrees 1-5"""
-    rng = np.random.default_rng(3)
-    starts = np.concatenate(([0], np.cumsum(SIZES)))
-    src, dst = [], []
-    for g, sz in enumerate(SIZES):
-        for t in range(sz):
-            if t % 7 == 3:
-                continue
-            for s_ in rng.choice(sz, size=min(sz, int(rng.integers(1, 6))), replace=False):
-                src.append(starts[g] + s_); dst.append(starts[g] + t)
-    order = np.argsort(np.array(dst), kind='stable')
-    ei = np.stack([np.array(src)[order], np.array(dst)[order]])
-    return ei, np.repeat(np.arange(len(SIZES)), SIZES), int(sum(SIZES))
 
 
 def csr_of(ei, n):
@@ -112,7 +81,7 @@ def check(out, ref, W, what):
 def test_parity_on_the_ragged_batch(mp, W, extra):
     ei, _, n = ragged_edges()
     rowptr, col = csr_of(ei, n)
-    ld = 128 * ((W + 127) // 128) + extra
+    ld = ld_of(W) + extra
     case = Case(mp, W, n, ld)
     rc, out = run(mp, case, rowptr, col, int(np.diff(rowptr).max()))
     assert rc == 0
@@ -145,27 +114,8 @@ def test_hub_at_the_degree_cap_runs_fused(mp):
     check(out, reference(case.P, case.Q, case.w2_64, case.b2_64, rowptr, col, W), W, f'hub of in-degree {cap}')
 
 
-def layer_inputs(mp, n, W, tw, nv, seed):
-    rng = np.random.default_rng(seed)
-    h = torch.tensor(rng.standard_normal((n, W)), dtype=torch.float32).cuda()
-    u = torch.tensor(rng.standard_normal((n, tw)), dtype=torch.float32).cuda()
-    pos = torch.tensor(rng.uniform(0, 1, (n, 1)), dtype=torch.float32).cuda()
-    var = torch.tensor(rng.uniform(0, 1, (n, nv)), dtype=torch.float32).cuda()
-    return h, u, pos, var
-
-
-def oracle_layer(main, gate, args, ei, batch):
-    args64 = [t.double().cpu().numpy() for t in args]
-    sd = lambda m: {k: v.detach().double().cpu().numpy() for k, v in m.state_dict().items()}
-    ref = O.mp_layer(O.layer_params(sd(main), ''), *args64, ei, batch, lin=True)
-    if gate is None:
-        return ref
-    tau = O.sigmoid(O.mp_layer(O.layer_params(sd(gate), ''), *args64, ei, batch, lin=True))
-    return (1.0 - tau) * args64[0] + tau * O.swish(ref)
-
-
 def test_hub_above_the_cap_is_refused_and_the_layer_takes_the_three_launches(mp):
-    from msmp_pde_amd.layers import _mp_layer_wide
+    from msmp_pde_amd.wide import _mp_layer_wide
     from msmp_pde_amd.graph import GraphStructure
     from msmp_pde_amd import _lib
     W, tw, nv = 164, 25, 2
@@ -183,7 +133,7 @@ def test_hub_above_the_cap_is_refused_and_the_layer_takes_the_three_launches(mp)
     assert gs.max_in_degree == cap + 1
     torch.manual_seed(9)
     main = mp.GNN_LayerLin(W, W, W, tw, nv).cuda()
-    h, u, pos, var = layer_inputs(mp, n, W, tw, nv, 4)
+    h, u, pos, var = layer_inputs(n, W, tw, nv, 4)
     with torch.no_grad():
         got = _mp_layer_wide(h, u, pos.reshape(-1), var, gs, main, None, 1e-5)
     e = np.abs(got.double().cpu().numpy() - oracle_layer(main, None, (h, u, pos, var), ei, batch)).max()
@@ -218,7 +168,7 @@ def test_more_tiles_than_resident_workgroups(mp):
 def test_runs_repeat_and_graphs_do_not_depend_on_the_batch(mp, W):
     ei, _, n = ragged_edges()
     rowptr, col = csr_of(ei, n)
-    ld = 128 * ((W + 127) // 128)
+    ld = ld_of(W)
     case = Case(mp, W, n, ld, seed=5)
     d = int(np.diff(rowptr).max())
     rc1, a = run(mp, case, rowptr, col, d)
@@ -264,7 +214,7 @@ def test_out_of_range_activation_raises_the_status(mp):
 
 @pytest.mark.parametrize('gated', [False, True])
 def test_layer_on_either_message_path(mp, gated, monkeypatch):
-    from msmp_pde_amd.layers import _mp_layer_wide
+    from msmp_pde_amd.wide import _mp_layer_wide
     from msmp_pde_amd.graph import GraphStructure
     from msmp_pde_amd import _lib
     W, tw, nv = 164, 25, 2
@@ -273,15 +223,10 @@ def test_layer_on_either_message_path(mp, gated, monkeypatch):
     torch.manual_seed(5)
     main = mp.GNN_LayerLin(W, W, W, tw, nv).cuda()
     gate = mp.GNN_LayerLin(W, W, W, tw, nv).cuda() if gated else None
-    h, u, pos, var = layer_inputs(mp, n, W, tw, nv, 3)
+    h, u, pos, var = layer_inputs(n, W, tw, nv, 3)
     ref = oracle_layer(main, gate, (h, u, pos, var), ei, batch)
     L = mp.lib()
-    real, calls = L.msmp_wide_message_f32, []
-
-    def counted(*a):
-        calls.append(1)
-        return real(*a)
-    monkeypatch.setattr(L, 'msmp_wide_message_f32', counted)
+    calls = counted(mp, monkeypatch, 'msmp_wide_message_f32')
     layer = lambda: _mp_layer_wide(h, u, pos.reshape(-1), var, gs, main, gate, 1e-5)
     with torch.no_grad():
         out1 = layer()

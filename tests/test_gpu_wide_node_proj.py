@@ -2,51 +2,23 @@
 the factorised message_net_1 of GNN_LayerLin (experiments/models_gnn.py:132-138) for both heads of a gated pair in one launch at any hidden
 width up to 256, against the two formulas in numpy float64 from the same fp32 inputs; its bitwise properties (run to run, independent of the
 nodes around a node and of where the node falls into the tiles), the bounds of its writes, the range status, the refusals by value, and the
-host paths that reach it: layers._mp_layer_wide and the two GLU solver classes.
+host paths that reach it: wide._mp_layer_wide and the two GLU solver classes.
 Bar: 1e-6 max(1, K / 156) on max|got - ref| / max(1, max|ref|) with K = W + tw + 1 + nv (1e-6 is the bar test_layer_pieces_vs_oracle holds
 this fp16-split arithmetic to at the 128-wide projection's K of about 156; the rounding sum grows at most linearly in K)."""
 import numpy as np
 import pytest
 import torch
 
-from helpers import synthetic_case
-from oracle import msmp_oracle as O
+from helpers import synthetic_case, ld_of, ragged_edges, layer_inputs, oracle_layer, counted
+from helpers import mp, restore_wide_switches       # noqa: F401  (fixtures)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('restore_wide_switches')]
 
 WIDTHS = [33, 96, 128, 130, 164, 192, 256]          # KT 2, 3, 4, 5, 6, 6, 8
 TAILS = [(25, 1), (25, 3), (50, 5), (100, 8)]       # 27, 29, 56, 109 feature columns: 2, 2, 4, 7 K = 16 steps (the cap is 128 columns)
 NODES = [1, 31, 64, 65, 200]                        # ragged last column block, ragged last tile
 N_MAX = 240
 EPS = 1e-5
-DEFAULTS = {}
-
-
-@pytest.fixture(scope='module')
-def mp():
-    import msmp_pde_amd
-    assert torch.cuda.is_available()
-    msmp_pde_amd.lib()
-    return msmp_pde_amd
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _defaults(mp):
-    for key in (b'wide_proj', b'wide_tail'):
-        DEFAULTS[key] = mp.lib().msmp_tune_query(key)
-
-
-@pytest.fixture(autouse=True)
-def _restore_switches(mp):
-    yield
-    for key in (b'wide_msg', b'split', b'lem_wide'):
-        mp.lib().msmp_tune(key, 1)
-    for key, value in DEFAULTS.items():
-        mp.lib().msmp_tune(key, value)
-
-
-def ld_of(W):
-    return 128 * ((W + 127) // 128)
 
 
 class Case(object):
@@ -211,56 +183,10 @@ def test_refusals_by_value_launch_nothing(mp):
     assert all((t == 7.5).all() for t in outs)
 
 
-def ragged_edges(sizes, seed=3):
-    """the graphs of test_wide_layer_pieces_vs_oracle: every seventh target without in-edges, in-degrees 1-5"""
-    rng = np.random.default_rng(seed)
-    starts = np.concatenate(([0], np.cumsum(sizes)))
-    src, dst = [], []
-    for g, sz in enumerate(sizes):
-        for t in range(sz):
-            if t % 7 == 3:
-                continue
-            for s_ in rng.choice(sz, size=min(sz, int(rng.integers(1, 6))), replace=False):
-                src.append(starts[g] + s_); dst.append(starts[g] + t)
-    order = np.argsort(np.array(dst), kind='stable')
-    ei = np.stack([np.array(src)[order], np.array(dst)[order]])
-    return ei, np.repeat(np.arange(len(sizes)), sizes), int(sum(sizes))
-
-
-def layer_inputs(n, W, tw, nv, seed):
-    rng = np.random.default_rng(seed)
-    h = torch.tensor(rng.standard_normal((n, W)), dtype=torch.float32).cuda()
-    u = torch.tensor(rng.standard_normal((n, tw)), dtype=torch.float32).cuda()
-    pos = torch.tensor(rng.uniform(0, 1, (n, 1)), dtype=torch.float32).cuda()
-    var = torch.tensor(rng.uniform(0, 1, (n, nv)), dtype=torch.float32).cuda()
-    return h, u, pos, var
-
-
-def oracle_layer(main, gate, args, ei, batch):
-    args64 = [t.double().cpu().numpy() for t in args]
-    sd = lambda m: {k: v.detach().double().cpu().numpy() for k, v in m.state_dict().items()}
-    ref = O.mp_layer(O.layer_params(sd(main), ''), *args64, ei, batch, lin=True)
-    if gate is None:
-        return ref
-    tau = O.sigmoid(O.mp_layer(O.layer_params(sd(gate), ''), *args64, ei, batch, lin=True))
-    return (1.0 - tau) * args64[0] + tau * O.swish(ref)
-
-
-def counted(mp, monkeypatch, name):
-    L = mp.lib()
-    real, calls = getattr(L, name), []
-
-    def entry(*a):
-        calls.append(1)
-        return real(*a)
-    monkeypatch.setattr(L, name, entry)
-    return calls
-
-
 @pytest.mark.parametrize('wide_tail', [0, 1])
 @pytest.mark.parametrize('gated', [False, True])
 def test_layer_takes_one_fused_projection_call(mp, gated, wide_tail, monkeypatch):
-    from msmp_pde_amd.layers import _mp_layer_wide
+    from msmp_pde_amd.wide import _mp_layer_wide
     from msmp_pde_amd.graph import GraphStructure
     from msmp_pde_amd import _lib
     W, tw, nv = 164, 25, 2

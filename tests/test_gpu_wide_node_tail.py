@@ -2,7 +2,7 @@
 and the gated blend of GNN_LayerLin (experiments/models_gnn.py:140-149, :129, :1486-1489) in one launch at any hidden width up to 256 on
 graphs of up to 128 nodes, against the formula in numpy float64 (O.node_update / O.instance_norm) from the same fp32 inputs; its bitwise
 properties (run to run, independent of the batch around a graph), the padding columns, the graph-size cap and the fall-back above it, the
-range status, and the host paths that reach it: layers._mp_layer_wide and the two GLU solver classes.
+range status, and the host paths that reach it: wide._mp_layer_wide and the two GLU solver classes.
 Bar: 5e-6 max(1, (2 W + nv) / 258) where every graph of more than one node has at least 30 nodes (5e-6 is the bar of test_node_tail_vs_oracle
 for this arithmetic at the 128-wide tail's K = 258; the rounding sum grows at most linearly in K), 2e-4 otherwise (InstanceNorm over a
 2-5 node graph amplifies fp32 rounding: that test's rule)."""
@@ -11,41 +11,14 @@ import pytest
 import torch
 
 from oracle import msmp_oracle as O
-from helpers import synthetic_case
+from helpers import synthetic_case, ld_of, ragged_edges, layer_inputs, oracle_layer, counted
+from helpers import mp, restore_wide_switches       # noqa: F401  (fixtures)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('restore_wide_switches')]
 
 WIDTHS = [33, 96, 128, 130, 164, 192, 256]          # KT 2, 3, 4, 5, 6, 6, 8
 BATCHES = [(2, [100, 100, 37, 1, 64]), (3, [128, 5, 90, 127]), (1, [2, 3, 33])]      # the batches of test_node_tail_vs_oracle
 EPS = 1e-5
-
-
-@pytest.fixture(scope='module')
-def mp():
-    import msmp_pde_amd
-    assert torch.cuda.is_available()
-    msmp_pde_amd.lib()
-    return msmp_pde_amd
-
-
-@pytest.fixture(autouse=True)
-def _restore_switches(mp):
-    yield
-    for key in (b'wide_tail', b'wide_msg', b'split', b'lem_wide'):
-        mp.lib().msmp_tune(key, 1)
-    mp.lib().msmp_tune(b'wide_tail', DEFAULT_WIDE_TAIL[0])
-
-
-DEFAULT_WIDE_TAIL = [None]
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _default(mp):
-    DEFAULT_WIDE_TAIL[0] = mp.lib().msmp_tune_query(b'wide_tail')
-
-
-def ld_of(W):
-    return 128 * ((W + 127) // 128)
 
 
 class Case(object):
@@ -169,54 +142,8 @@ def test_padding_columns_are_zero_and_nothing_else_is_written(mp):
         check(case, out, gated, 'poisoned buffer')
 
 
-def ragged_edges(sizes, seed=3):
-    """the graphs of test_wide_layer_pieces_vs_oracle: every seventh target without in-edges, in-degrees 1-5"""
-    rng = np.random.default_rng(seed)
-    starts = np.concatenate(([0], np.cumsum(sizes)))
-    src, dst = [], []
-    for g, sz in enumerate(sizes):
-        for t in range(sz):
-            if t % 7 == 3:
-                continue
-            for s_ in rng.choice(sz, size=min(sz, int(rng.integers(1, 6))), replace=False):
-                src.append(starts[g] + s_); dst.append(starts[g] + t)
-    order = np.argsort(np.array(dst), kind='stable')
-    ei = np.stack([np.array(src)[order], np.array(dst)[order]])
-    return ei, np.repeat(np.arange(len(sizes)), sizes), int(sum(sizes))
-
-
-def layer_inputs(n, W, tw, nv, seed):
-    rng = np.random.default_rng(seed)
-    h = torch.tensor(rng.standard_normal((n, W)), dtype=torch.float32).cuda()
-    u = torch.tensor(rng.standard_normal((n, tw)), dtype=torch.float32).cuda()
-    pos = torch.tensor(rng.uniform(0, 1, (n, 1)), dtype=torch.float32).cuda()
-    var = torch.tensor(rng.uniform(0, 1, (n, nv)), dtype=torch.float32).cuda()
-    return h, u, pos, var
-
-
-def oracle_layer(main, gate, args, ei, batch):
-    args64 = [t.double().cpu().numpy() for t in args]
-    sd = lambda m: {k: v.detach().double().cpu().numpy() for k, v in m.state_dict().items()}
-    ref = O.mp_layer(O.layer_params(sd(main), ''), *args64, ei, batch, lin=True)
-    if gate is None:
-        return ref
-    tau = O.sigmoid(O.mp_layer(O.layer_params(sd(gate), ''), *args64, ei, batch, lin=True))
-    return (1.0 - tau) * args64[0] + tau * O.swish(ref)
-
-
-def counted_entry(mp, monkeypatch):
-    L = mp.lib()
-    real, calls = L.msmp_wide_node_tail_f32, []
-
-    def counted(*a):
-        calls.append(1)
-        return real(*a)
-    monkeypatch.setattr(L, 'msmp_wide_node_tail_f32', counted)
-    return calls
-
-
 def test_a_graph_above_the_cap_is_refused_and_the_layer_takes_the_gemms(mp, monkeypatch):
-    from msmp_pde_amd.layers import _mp_layer_wide
+    from msmp_pde_amd.wide import _mp_layer_wide
     from msmp_pde_amd.graph import GraphStructure
     W, tw, nv = 164, 25, 2
     L = mp.lib()
@@ -234,7 +161,7 @@ def test_a_graph_above_the_cap_is_refused_and_the_layer_takes_the_gemms(mp, monk
     main, gate = mp.GNN_LayerLin(W, W, W, tw, nv).cuda(), mp.GNN_LayerLin(W, W, W, tw, nv).cuda()
     h, u, pos, var = layer_inputs(n, W, tw, nv, 4)
     L.msmp_tune(b'wide_tail', 1)
-    calls = counted_entry(mp, monkeypatch)
+    calls = counted(mp, monkeypatch, 'msmp_wide_node_tail_f32')
     with torch.no_grad():
         got = _mp_layer_wide(h, u, pos.reshape(-1), var, gs, main, gate, EPS)
     assert not calls                                          # the host asks msmp_wide_node_tail_max_graph_nodes first
@@ -257,7 +184,7 @@ def test_out_of_range_row_raises_the_status(mp):
 
 @pytest.mark.parametrize('gated', [False, True])
 def test_layer_takes_one_fused_tail_call(mp, gated, monkeypatch):
-    from msmp_pde_amd.layers import _mp_layer_wide
+    from msmp_pde_amd.wide import _mp_layer_wide
     from msmp_pde_amd.graph import GraphStructure
     from msmp_pde_amd import _lib
     W, tw, nv = 164, 25, 2
@@ -270,7 +197,7 @@ def test_layer_takes_one_fused_tail_call(mp, gated, monkeypatch):
     h, u, pos, var = layer_inputs(n, W, tw, nv, 3)
     ref = oracle_layer(main, gate, (h, u, pos, var), ei, batch)
     L = mp.lib()
-    calls = counted_entry(mp, monkeypatch)
+    calls = counted(mp, monkeypatch, 'msmp_wide_node_tail_f32')
     layer = lambda: _mp_layer_wide(h, u, pos.reshape(-1), var, gs, main, gate, EPS)
     with torch.no_grad():
         L.msmp_tune(b'wide_tail', 1)
@@ -304,7 +231,7 @@ def test_glu_solver_forward_on_either_tail_path(mp, kind, exp, monkeypatch):
     model = getattr(mp, kind)(case.pde, time_window=25, eq_variables=case.eqv, hidden_layer=2).cuda().eval()
     graph = case.graph.to('cuda')
     L = mp.lib()
-    calls = counted_entry(mp, monkeypatch)
+    calls = counted(mp, monkeypatch, 'msmp_wide_node_tail_f32')
     with torch.no_grad():
         L.msmp_tune(b'wide_tail', 1)
         out1 = model(graph)

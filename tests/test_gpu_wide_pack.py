@@ -12,19 +12,13 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import mp       # noqa: F401  (fixture)
+
 pytestmark = pytest.mark.gpu
 
 WIDTHS = [24, 40]
 LANE, J = np.meshgrid(np.arange(64), np.arange(8), indexing='ij')       # [lane 64][j 8] of one fragment
 C, HH = LANE & 31, LANE >> 5
-
-
-@pytest.fixture(scope='module')
-def mp():
-    import msmp_pde_amd
-    assert torch.cuda.is_available()
-    msmp_pde_amd.lib()
-    return msmp_pde_amd
 
 
 def k_natural(ks):
