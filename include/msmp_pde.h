@@ -52,10 +52,11 @@ extern "C" {
 
 typedef void* msmp_stream_t;
 
-/* ABI version: 400 = round 4 (msmp_tiles_t: listed, period_tiles, period_nodes; msmp_build_tiles writes 3 statistics);
+/* ABI version: 410 = msmp_mp_layer_decode_f32 and msmp_decoder_t removed;
+ * 400 = round 4 (msmp_tiles_t: listed, period_tiles, period_nodes; msmp_build_tiles writes 3 statistics);
  * 300 = round 3 (msmp_last_status, msmp_tiles_t checked on every entry point that takes one).  Bumped whenever a
  * prototype or a blob layout changes; the ctypes host refuses a library whose version is not the one it was written for. */
-#define MSMP_ABI_VERSION 400
+#define MSMP_ABI_VERSION 410
 int msmp_version(void);
 const char* msmp_last_error(void);
 
@@ -75,18 +76,20 @@ const char* msmp_last_error(void);
 #define MSMP_STATUS_NODE_SATURATED 2
 #define MSMP_STATUS_NONFINITE      4
 int msmp_last_status(int* flags_out, int reset);
-/* Knobs for A/B measurements and validation (not part of the data contract):
+/* Knobs for A/B measurements and validation (not part of the data contract).  Every key below can be set and queried; each entry
+ * names its default.  msmp_tune returns MSMP_ERR_ARG for NULL, for a key that is not listed ("unknown key") and for a value outside
+ * a key's stated range (the value stays as it was); msmp_tune_query returns 0 for NULL and for a key that is not listed.
  *   "split"   1 (default): the GEMMs of the node / edge / LEM kernels run on the fp16 matrix pipe with a 2-way
  *             fp16 split of both operands (fp32-class accuracy); 0: the fp32-MFMA kernels.  It also selects
  *             the LEM kernel: 1 the weight-stationary lem_encoder_ws3_kernel, 0 the fp32 lem_encoder_kernel.
- *   "edge_nb" 0 auto, 1 / 2 force the 128- / 256-edge tile of the factorised message kernel.
+ *   "edge_nb" 0 (default) auto, 1 / 2 force the 128- / 256-edge tile of the factorised message kernel.
  *   "tile"    2 (default): with node tiles that are at least 60 % full (>= 76 edges per tile on average), project P / Q inside the message
  *             kernel, else the gather kernels; 3: the same regardless of the fill; 1: msmp_node_project_f32 + tile kernel on the
  *             staged P / Q rows; 0: ignore the tiles (gather kernels).
  *   "bwd_gemm" 1 (default) / 2: msmp_mp_layer_bwd_f32 runs its row GEMMs on its own bf16x3 MFMA kernels (fused bias / Swish / dSwish epilogues;
  *             128-row workgroups from 32 768 rows on, 32-row workgroups whose waves split the output channels below);
  *             0: rocblas_sgemm + separate epilogue passes (A/B runs only: librocblas is loaded on first use).
- *   "lem_share" k (default 1): k LEM launches share the GPU (sub-batches on k streams): each plans its rounds for CUs / k.
+ *   "lem_share" k (default 1; accepted: 1 to 16): k LEM launches share the GPU (sub-batches on k streams): each plans its rounds for CUs / k.
  *   "lem_tail" 1 (default): the LEM launch ends with a round of one-tile workgroups where that saves >= 0.3 of a round; 0: three-tile
  *             workgroups only (same bits either way).
  *   "lem_wide" 1 (default): the host's no-grad LEM at widths other than 128 is one msmp_lem_encoder_wide_f32 launch; 0: the loop of two
@@ -104,11 +107,14 @@ int msmp_last_status(int* flags_out, int reset);
  *             (the entry itself does not read the key).  The host takes the fused launch only while "wide_msg", "split" and "lem_wide" are 1
  *             as well, so each of those keeps selecting the path it selected before this kernel.
  *   "tile_arith" 1 (default): ranged tiles take their node rows by arithmetic on tile_halo; 0: always through the node list.
+ *   "tile_align" 0 (default): the host cuts the node tiles of a batch of identical graphs at graph boundaries only where tile_nodes divides
+ *             the graph size; 1: also where it does not (bitwise graph-order / sharding equivariance on knn graphs, 11-20 % more tiles
+ *             there).  No entry point reads the key.
  *   "tail"    1 (default): msmp_mp_layer_f32 uses msmp_node_tail_f32 for graphs of up to 128 nodes; 0: the piecewise kernels.
  *   "pair"    gated pair: both heads' projection / message kernels in one launch each (bit-identical results): 0 never,
  *             1 (default) for batches of up to 65 536 nodes, where a step is bound by the latency of its ~60 dependent launches, 2 always. */
 int msmp_tune(const char* key, int value);
-int msmp_tune_query(const char* key);      /* current value of "split", "tail", "pair", "bwd_gemm", "tile", "tile_arith", "lem_wide", "wide_msg", "wide_tail", "wide_proj", ... (0 for unknown keys) */
+int msmp_tune_query(const char* key);
 
 /* ---------------------------------------------------------------------------------------------
  * Weights
@@ -307,30 +313,6 @@ int msmp_mp_layer_f32(const float* h, const float* u, const float* pos, const fl
                       const float* packed_gate, int mode,
                       float eps, float* h_out, void* workspace, size_t workspace_bytes,
                       msmp_stream_t stream);
-
-/* The LAST layer (pair) of a 1-D solver with the decoder as the node tail's epilogue ("decoder fusion into
- * the last layer's epilogue"; experiments/models_gnn.py:1365-1375: the loop's last iteration, then output_mlp and the Euler update):
- * h_out is still written (the rows are read back from L2 by the workgroup that wrote them, not from HBM), dec->out receives
- * out = u[:, -1] + cumsum(dt) * Conv1d(8,1,k2)(Swish(Conv1d(1,8,k1,stride s1)(h_out))) (dec->u == NULL: the decoder output alone),
- * bit-identical to msmp_mp_layer_f32 followed by msmp_decoder_f32.  Returns MSMP_ERR_UNSUPPORTED where the fused tail does not
- * apply (time_window != 25, graphs of more than 128 nodes, msmp_tune "split" / "tail" off): call the two entry points then. */
-typedef struct {
-    const float* w1;             /* output_mlp[0].weight [8,1,k1] */
-    const float* b1;             /* output_mlp[0].bias   [8]      */
-    const float* w2;             /* output_mlp[2].weight [1,8,k2] */
-    const float* b2;             /* output_mlp[2].bias   [1]      */
-    const float* u;              /* [N, time_window] or NULL      */
-    float dt;
-    int32_t time_window;
-    float* out;                  /* [N, time_window]              */
-} msmp_decoder_t;
-int msmp_mp_layer_decode_f32(const float* h, const float* u, const float* pos, const float* vars,
-                             const float* feat, const int32_t* rowptr, const int32_t* col, const int32_t* tgt,
-                             const msmp_tiles_t* tiles, const int32_t* graph_ptr, int64_t n_nodes, int64_t n_edges, int64_t n_graphs,
-                             int max_in_degree, int max_graph_nodes, int tw, int nv, const float* packed_main,
-                             const float* packed_gate, int mode,
-                             float eps, float* h_out, const msmp_decoder_t* dec, void* workspace, size_t workspace_bytes,
-                             msmp_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * LEM node encoder (replaces the absent `lem_cuda` extension)

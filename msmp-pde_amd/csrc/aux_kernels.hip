@@ -1,6 +1,8 @@
 // HBM-bound pieces of the message-passing layer: weight packing, mean aggregation (row L2),
 // InstanceNorm (row L4), gate blend (row L5), and the whole-layer entry point that chains the pieces.
+#include <limits.h>
 #include <stdarg.h>
+#include <string.h>
 #include "graph_norm.h"
 #include <vector>
 #include "mfma_tiles.h"
@@ -446,6 +448,60 @@ extern "C" int msmp_last_status(int* flags_out, int reset) {
 extern "C" int msmp_version(void) { return MSMP_ABI_VERSION; }
 extern "C" const char* msmp_last_error(void) { return g_err; }
 
+// ---- tuning switches (msmp_tune / msmp_tune_query; inside the library msmp_tune_get) --------------------------------------------
+// One row per switch; include/msmp_pde.h documents the same keys and defaults (tests/test_host_cpu.py compares the two).  The
+// measurements behind a default stand where the switch is read.
+struct TuneRow {
+    const char* key;
+    int value;          // current
+    int def;            // of a fresh library
+    int lo, hi;         // accepted values; anything else is refused and leaves `value` alone
+    bool flag;          // stored as value != 0
+    constexpr TuneRow(const char* k, int d, int l, int h, bool f) : key(k), value(d), def(d), lo(l), hi(h), flag(f) {}
+};
+#define ANY_INT INT_MIN, INT_MAX, false
+#define ON_OFF INT_MIN, INT_MAX, true
+static TuneRow g_tune[] = {
+    {"split", 1, ANY_INT},       // fp16-split matrix path (default); 0 selects the fp32-MFMA kernels
+    {"edge_nb", 0, ANY_INT},     // 0 = automatic, 1 / 2 = force the tile size of the factorised kernel
+    {"pair", 1, ANY_INT},        // gated pair: both heads' projection / message kernels in one launch each: 0 never, 1 up to PAIR_MAX_NODES nodes, 2 always
+    {"tile", 2, ANY_INT},        // node tiles (tile_kernels.hip): 2 fold the projections into the message kernel, 1 staged P / Q rows, 0 off
+    {"tile_arith", 1, ANY_INT},  // ranged tiles: slot -> node arithmetically (tile_halo) instead of through the node list
+    {"tile_align", 0, ANY_INT},  // host layer: cut node tiles at graph boundaries also where tile_nodes does not divide the graph size (bitwise graph-order / sharding equivariance on knn graphs, ~11-20 % more tiles there)
+    {"bwd_gemm", 1, ANY_INT},    // layer backward: row GEMMs on rows_gemm_kernel (bf16x3 MFMA, fused epilogues); 0: rocblas_sgemm + separate passes
+    {"tail", 1, ANY_INT},        // fused node tail (msmp_node_tail_f32) inside msmp_mp_layer_f32; 0 chains the pieces
+    {"lem_share", 1, 1, 16, false},  // k LEM launches share the GPU (sub-batches on k streams): a launch plans for CUs / k
+    {"lem_tail", 1, ON_OFF},     // 0: every workgroup of the ws3 LEM kernel takes three tiles (no round of one-tile workgroups)
+    {"lem_wide", 1, ON_OFF},     // 0: the host keeps the per-step GEMM + pointwise loop at widths other than 128
+    {"wide_msg", 1, ON_OFF},     // 0: the host layer keeps gather + row GEMM + scatter at widths other than 128
+    {"wide_tail", 0, ON_OFF},    // 1: the host layer takes msmp_wide_node_tail_f32 at widths other than 128 (wide_node_tail_kernel.hip)
+    {"wide_proj", 0, ON_OFF},    // 1: the host layer takes msmp_wide_node_proj_f32 at widths other than 128 (wide_node_proj_kernel.hip)
+};
+#undef ANY_INT
+#undef ON_OFF
+
+static TuneRow* tune_row(const char* key) {
+    if (key)
+        for (TuneRow& r : g_tune)
+            if (!strcmp(key, r.key)) return &r;
+    return nullptr;
+}
+
+int msmp_tune_get(const char* key) {
+    const TuneRow* r = tune_row(key);
+    return r ? r->value : 0;
+}
+
+extern "C" int msmp_tune_query(const char* key) { return msmp_tune_get(key); }
+
+extern "C" int msmp_tune(const char* key, int value) {
+    TuneRow* r = tune_row(key);
+    MSMP_REQUIRE(r, MSMP_ERR_ARG, "msmp_tune: unknown key");
+    MSMP_REQUIRE(value >= r->lo && value <= r->hi, MSMP_ERR_ARG, "msmp_tune: %s = %d is out of range (%d to %d)", key, value, r->lo, r->hi);
+    r->value = r->flag ? value != 0 : value;
+    return MSMP_OK;
+}
+
 extern "C" int64_t msmp_packed_layer_floats(int tw, int nv) {
     if (tw <= 0 || nv < 1 || nv > MSMP_MAX_VARS) return -1;
     return packed_layout(tw, nv).total;
@@ -525,43 +581,12 @@ extern "C" size_t msmp_mp_layer_workspace_bytes(int64_t n_nodes, int64_t n_edges
     return msg + nod * 6 + 256;
 }
 
-static int mp_layer_impl(const float* h, const float* u, const float* pos, const float* vars, const float* feat,
-                         const int32_t* rowptr, const int32_t* col, const int32_t* tgt, const msmp_tiles_t* tiles,
-                         const int32_t* graph_ptr,
-                         int64_t n_nodes, int64_t n_edges, int64_t n_graphs, int max_in_degree, int max_graph_nodes,
-                         int tw, int nv, const float* packed_main, const float* packed_gate, int mode, float eps, float* h_out,
-                         const msmp_decoder_t* dec, void* workspace, size_t workspace_bytes, msmp_stream_t stream);
-
 extern "C" int msmp_mp_layer_f32(const float* h, const float* u, const float* pos, const float* vars, const float* feat,
                                  const int32_t* rowptr, const int32_t* col, const int32_t* tgt, const msmp_tiles_t* tiles,
                                  const int32_t* graph_ptr,
                                  int64_t n_nodes, int64_t n_edges, int64_t n_graphs, int max_in_degree, int max_graph_nodes,
                                  int tw, int nv, const float* packed_main, const float* packed_gate, int mode, float eps, float* h_out,
                                  void* workspace, size_t workspace_bytes, msmp_stream_t stream) {
-    return mp_layer_impl(h, u, pos, vars, feat, rowptr, col, tgt, tiles, graph_ptr, n_nodes, n_edges, n_graphs, max_in_degree, max_graph_nodes, tw, nv,
-                         packed_main, packed_gate, mode, eps, h_out, nullptr, workspace, workspace_bytes, stream);
-}
-
-extern "C" int msmp_mp_layer_decode_f32(const float* h, const float* u, const float* pos, const float* vars, const float* feat,
-                                        const int32_t* rowptr, const int32_t* col, const int32_t* tgt, const msmp_tiles_t* tiles,
-                                        const int32_t* graph_ptr,
-                                        int64_t n_nodes, int64_t n_edges, int64_t n_graphs, int max_in_degree, int max_graph_nodes,
-                                        int tw, int nv, const float* packed_main, const float* packed_gate, int mode, float eps, float* h_out,
-                                        const msmp_decoder_t* dec, void* workspace, size_t workspace_bytes, msmp_stream_t stream) {
-    MSMP_REQUIRE(dec, MSMP_ERR_ARG, "msmp_mp_layer_decode_f32: null decoder description");
-    MSMP_REQUIRE(dec->time_window == 25 && msmp_tune_get("split") && msmp_tune_get("tail") && max_graph_nodes > 0 && max_graph_nodes <= 128,
-                 MSMP_ERR_UNSUPPORTED, "msmp_mp_layer_decode_f32: the fused tail does not apply (time_window %d, max_graph_nodes %d)", dec->time_window,
-                 max_graph_nodes);
-    return mp_layer_impl(h, u, pos, vars, feat, rowptr, col, tgt, tiles, graph_ptr, n_nodes, n_edges, n_graphs, max_in_degree, max_graph_nodes, tw, nv,
-                         packed_main, packed_gate, mode, eps, h_out, dec, workspace, workspace_bytes, stream);
-}
-
-static int mp_layer_impl(const float* h, const float* u, const float* pos, const float* vars, const float* feat,
-                         const int32_t* rowptr, const int32_t* col, const int32_t* tgt, const msmp_tiles_t* tiles,
-                         const int32_t* graph_ptr,
-                         int64_t n_nodes, int64_t n_edges, int64_t n_graphs, int max_in_degree, int max_graph_nodes,
-                         int tw, int nv, const float* packed_main, const float* packed_gate, int mode, float eps, float* h_out,
-                         const msmp_decoder_t* dec, void* workspace, size_t workspace_bytes, msmp_stream_t stream) {
     MSMP_REQUIRE(h && u && pos && vars && rowptr && col && tgt && graph_ptr && packed_main && h_out && workspace,
                  MSMP_ERR_ARG, "msmp_mp_layer_f32: null pointer");
     MSMP_REQUIRE(h_out != h, MSMP_ERR_ARG, "msmp_mp_layer_f32: h_out may not alias h");
@@ -588,7 +613,8 @@ static int mp_layer_impl(const float* h, const float* u, const float* pos, const
     // empty (32 node slots are used up before 128 edges: knn graphs of in-degree 3 on a scattered grid, RPU: 66 edges per tile)
     // run the untiled kernels (measured at 2048 graphs, ms per rollout step, tiled / untiled: RPU 7.00 / 6.77, WE3 at 84 edges
     // per tile 5.72 / 5.92, E2 at 123: 6.6 / 7.1).  "tile" 3 forces the tiles.
-    int tile_mode = (tiles && n_edges > 0 && msmp_tune_get("split")) ? msmp_tune_get("tile") : 0;
+    const bool split = msmp_tune_get("split") != 0;
+    int tile_mode = (tiles && n_edges > 0 && split) ? msmp_tune_get("tile") : 0;
     if (tile_mode == 2 && n_edges < (int64_t)76 * tiles->n_tiles) tile_mode = 0;
     if (tile_mode == 3) tile_mode = 2;
     auto aggregate = [&](const float* packed, float* agg) -> int {
@@ -611,9 +637,10 @@ static int mp_layer_impl(const float* h, const float* u, const float* pos, const
         return r ? r : msmp_scatter_mean_f32(msg, rowptr, n_nodes, agg, stream);
     };
     // node tail (rows L3-L5): one launch per layer when the graphs fit a workgroup (update head(s) + InstanceNorm + blend)
-    if (msmp_tune_get("split") && msmp_tune_get("tail") && max_graph_nodes > 0 && max_graph_nodes <= 128) {
+    if (split && msmp_tune_get("tail") && max_graph_nodes > 0 && max_graph_nodes <= 128) {
         rc = MSMP_ERR_UNSUPPORTED;
-        if (gated && fused && !dense && tile_mode == 2 && msmp_tune_get("pair") && (msmp_tune_get("pair") == 2 || n_nodes <= 65536))
+        const int pair = msmp_tune_get("pair");
+        if (gated && fused && !dense && tile_mode == 2 && pair && (pair == 2 || n_nodes <= 65536))
             rc = msmp_edge_aggregate_tiled_pair(h, u, pos, vars, feat, rowptr, tiles, n_nodes, n_edges, tw, nv, packed_gate, packed_main, pre_gate,
                                                 agg, stream);      // small batches: both heads in one launch
         else if (gated && fused && !dense && !tile_mode)       // small batches: both heads per launch (projection, then message + mean)
@@ -623,10 +650,9 @@ static int mp_layer_impl(const float* h, const float* u, const float* pos, const
             if (gated && (rc = aggregate(packed_gate, pre_gate))) return rc;       // pre_gate doubles as the gate head's aggregate
             if ((rc = aggregate(packed_main, agg))) return rc;
         } else if (rc) return rc;
-        return msmp_node_tail_impl(h, agg, gated ? pre_gate : nullptr, vars, graph_ptr, n_nodes, n_graphs, max_graph_nodes, nv,
-                                   packed_main, packed_gate, mode, eps, h_out, dec, stream);
+        return msmp_node_tail_f32(h, agg, gated ? pre_gate : nullptr, vars, graph_ptr, n_nodes, n_graphs, max_graph_nodes, nv,
+                                  packed_main, packed_gate, mode, eps, h_out, stream);
     }
-    MSMP_REQUIRE(!dec, MSMP_ERR_UNSUPPORTED, "msmp_mp_layer_decode_f32: the fused tail does not apply");
     if (gated) {
         if ((rc = aggregate(packed_gate, agg))) return rc;
         if ((rc = msmp_node_update_f32(h, agg, vars, n_nodes, nv, packed_gate, MSMP_LAYER_LIN, pre_gate, stream))) return rc;

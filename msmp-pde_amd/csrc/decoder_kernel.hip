@@ -1,19 +1,31 @@
-// Decoder of the 1-D solver classes fused into one pass:
-//   diff = Conv1d(8 -> 1, k2)( Swish( Conv1d(1 -> 8, k1, stride s1)( h[:, None, :] ) ) )      experiments/models_gnn.py:210-224, 278
-//   out  = u[:, -1:] + cumsum(dt)[None, :] * diff                                              :275-279
-// One node per lane, the 128-channel row h[n] in registers; the eight intermediate channels are produced
-// one at a time (L1 = (128-k1)/s1+1 values), passed through Swish and folded into the tw outputs at once,
-// so nothing but h (read) and out (write) touches memory.  Weights are indexed with compile-time
-// constants: the compiler keeps them in SGPRs (scalar loads).  ~7.7 kFMA per node: VALU work, ~3 GFLOP per
-// E2-2048 batch; HBM traffic N*(512 + 4 + 100) bytes = 126 MB.
+// Decoders of the solver classes, each fused into one pass: nothing but h (read) and out (write)
+// touches memory.  1-D classes (experiments/models_gnn.py:210-224, 275-279):
+//   diff = Conv1d(8 -> 1, k2)( Swish( Conv1d(1 -> 8, k1, stride s1)( h[:, None, :] ) ) )
+//   out  = u[:, -1:] + cumsum(dt)[None, :] * diff
+// ~7.7 kFMA per node: VALU work, ~3 GFLOP per E2-2048 batch; HBM traffic N*(512 + 4 + 100) bytes = 126 MB.  Weights are indexed
+// with compile-time constants: the compiler keeps them in SGPRs (scalar loads).
+// Both kernels give a node to EIGHT lanes, split by position: a lane that kept a whole row and both intermediate arrays in registers
+// would need 256 VGPRs + 250 AGPRs, one wave per SIMD.
 #include "msmp_common.h"
-#include "decoder_body.h"
 
 namespace msmp {
 
+template <int TW, int K1, int S1, int K2>
+struct DecSplit {
+    static constexpr int L1 = (H - K1) / S1 + 1;
+    static constexpr int PP = (L1 + 7) / 8;                          // intermediate positions per lane
+    static constexpr int XW = (PP - 1) * S1 + K1;                    // row values a lane needs
+    static constexpr int OPL = TW > 32 ? 8 : 4;                      // consecutive outputs per lane (multiple of 4: aligned 16-byte LDS reads)
+    static constexpr int MW = OPL + K2 - 1;                          // intermediate values per channel a lane needs for them
+    static constexpr int MW4 = (MW + 3) / 4;
+    static constexpr int LP = ((7 * OPL + 4 * MW4 > L1 ? 7 * OPL + 4 * MW4 : L1) + 3) / 4 * 4 + 4;      // padded row of the LDS table
+    static constexpr int NODES = 8 * LP * 4 * 32 <= 49152 ? 32 : 16;  // nodes per workgroup (LDS <= 48 KB)
+    static_assert(L1 - K2 + 1 == TW && 8 * OPL >= TW, "decoder geometry");
+};
+
 struct DecArgs {
     const float* h;      // [N,128]
-    const float* u;      // [N,tw]
+    const float* u;      // [N,tw] (nullptr: the decoder output alone, what MSSMP_PDE_Solver_sub returns, models_gnn.py:1679-1682)
     long n_nodes;
     const float* w1;     // [8][k1]
     const float* b1;     // [8]
@@ -23,71 +35,84 @@ struct DecArgs {
     float* out;          // [N,tw]
 };
 
+// ----------------------------------------------------------------------------------------------
+// Lane q (0..7) of a node computes the intermediate positions [q PP, (q + 1) PP) of all eight channels from a 26-28-value window of
+// the row, the node's 8 x L1 intermediates meet in LDS (the node's [8][LP] table), and lane q then forms OPL consecutive outputs from
+// a (OPL + K2 - 1)-value window per channel.  < 100 registers, three workgroups per CU.
+// Summation order: every sum starts from its bias and adds its taps j = 0 .. k - 1 in ascending order with fmaf, one intermediate
+// channel c = 0 .. 7 after the other into the output; cumsum(dt) is formed by repeated float32 addition like torch.cumsum on the device.
+// decoder_split_node is lane q of node n (row: the node's 128 floats, of the last node for the lanes past the end, which are not
+// `live` and write nothing; mrow: the node's table); of `a` it takes the weights, u, dt and out.
+// ----------------------------------------------------------------------------------------------
 template <int TW, int K1, int S1, int K2>
-__global__ __launch_bounds__(256) void decoder_kernel(DecArgs a) {
-    constexpr int L1 = (H - K1) / S1 + 1;
-    static_assert(L1 - K2 + 1 == TW, "decoder geometry");
-    const long n = (long)blockIdx.x * 256 + threadIdx.x;
-    if (n >= a.n_nodes) return;
-    float x[H];
-    const f32x4* hp = reinterpret_cast<const f32x4*>(a.h + (size_t)n * H);
+__device__ __forceinline__ void decoder_split_node(const float* row, float* mrow, int q, bool live, long n, const DecArgs& a) {
+    using G = DecSplit<TW, K1, S1, K2>;
+    constexpr int L1 = G::L1, PP = G::PP, XW = G::XW, OPL = G::OPL, MW4 = G::MW4, LP = G::LP;
+    const int p0 = q * PP;
+    float x[XW];
+    {
+        const int x0 = p0 * S1;
 #pragma unroll
-    for (int i = 0; i < H / 4; ++i) {
-        const f32x4 v = hp[i];
-        x[4 * i] = v[0]; x[4 * i + 1] = v[1]; x[4 * i + 2] = v[2]; x[4 * i + 3] = v[3];
+        for (int i = 0; i < XW; ++i) x[i] = row[x0 + i < H ? x0 + i : H - 1];
     }
-    float o[TW];
-    const float bias2 = a.b2[0];
-#pragma unroll
-    for (int t = 0; t < TW; ++t) o[t] = bias2;
 #pragma unroll 1
     for (int c = 0; c < 8; ++c) {
-        float w1c[K1], w2c[K2];
+        float w1c[K1];
 #pragma unroll
         for (int j = 0; j < K1; ++j) w1c[j] = a.w1[c * K1 + j];
+        const float bc = a.b1[c];
+        float s[PP];
+#pragma unroll
+        for (int pp = 0; pp < PP; ++pp) s[pp] = bc;
+#pragma unroll
+        for (int j = 0; j < K1; ++j)
+#pragma unroll
+            for (int pp = 0; pp < PP; ++pp) s[pp] = fmaf(w1c[j], x[pp * S1 + j], s[pp]);
+#pragma unroll
+        for (int pp = 0; pp < PP; ++pp)
+            if (p0 + pp < L1) mrow[c * LP + p0 + pp] = swishf(s[pp]);
+    }
+    __syncthreads();        // every lane of a node's table has written before any reads
+    // ---- outputs t0 .. t0 + OPL - 1 of this lane -------------------------------------------------------------------------
+    const int t0 = q * OPL;
+    float o[OPL];
+    const float bias2 = a.b2[0];
+#pragma unroll
+    for (int i = 0; i < OPL; ++i) o[i] = bias2;
+#pragma unroll 1
+    for (int c = 0; c < 8; ++c) {
+        float w2c[K2];
 #pragma unroll
         for (int j = 0; j < K2; ++j) w2c[j] = a.w2[c * K2 + j];
-        const float bc = a.b1[c];
-        float mid[L1];
+        float m[4 * MW4];
 #pragma unroll
-        for (int p = 0; p < L1; ++p) {
-            float s = bc;
-#pragma unroll
-            for (int j = 0; j < K1; ++j) s = fmaf(w1c[j], x[p * S1 + j], s);
-            mid[p] = swishf(s);
+        for (int i = 0; i < MW4; ++i) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(mrow + c * LP + t0 + 4 * i);
+            m[4 * i] = v[0]; m[4 * i + 1] = v[1]; m[4 * i + 2] = v[2]; m[4 * i + 3] = v[3];
         }
 #pragma unroll
-        for (int t = 0; t < TW; ++t) {
-            float s = o[t];
+        for (int j = 0; j < K2; ++j)
 #pragma unroll
-            for (int j = 0; j < K2; ++j) s = fmaf(w2c[j], mid[t + j], s);
-            o[t] = s;
-        }
+            for (int i = 0; i < OPL; ++i) o[i] = fmaf(w2c[j], m[i + j], o[i]);
     }
+    if (!live || t0 >= TW) return;
     float* op = a.out + (size_t)n * TW;
-    if (a.u == nullptr) {                   // the decoder output alone (MSSMP_PDE_Solver_sub, models_gnn.py:1679-1682)
+    if (a.u == nullptr) {
 #pragma unroll
-        for (int t = 0; t < TW; ++t) op[t] = o[t];
+        for (int i = 0; i < OPL; ++i)
+            if (t0 + i < TW) op[t0 + i] = o[i];
         return;
     }
     const float ul = a.u[(size_t)n * TW + TW - 1];
     float tcum = 0.f;
+    for (int t = 0; t < t0; ++t) tcum += a.dt;          // cumsum of a constant, float32 partial sums like torch.cumsum on the device
 #pragma unroll
-    for (int t = 0; t < TW; ++t) {
-        tcum += a.dt;                       // cumsum of a constant, float32 like torch.cumsum on the device
-        op[t] = ul + tcum * o[t];
+    for (int i = 0; i < OPL; ++i) {
+        tcum += a.dt;
+        if (t0 + i < TW) op[t0 + i] = ul + tcum * o[i];
     }
 }
 
-// ----------------------------------------------------------------------------------------------
-// The same decoder with EIGHT lanes per node, split by position (default since round 3).  decoder_kernel above keeps a node's
-// whole row and both intermediate arrays in one lane's registers: 256 VGPRs + 250 AGPRs, ONE wave per SIMD, which issues at most one
-// vector instruction per 4.4 clocks (scripts/micro/valu_issue.hip) on a SIMD that takes two -- 112 us per launch at 2048 graphs for
-// 8.9 k instructions per wave, in 3.125 -> 4 rounds.  Here lane q of a node computes the intermediate positions
-// [q PP, (q + 1) PP) of all eight channels from a 26-28-value window of the row, the node's 8 x L1 intermediates meet in LDS,
-// and lane q then forms OPL consecutive outputs from a (OPL + K2 - 1)-value window per channel.  < 100 registers, three
-// workgroups per CU.  The taps of every sum are added in the order of decoder_kernel: the same bits.
-// ----------------------------------------------------------------------------------------------
 template <int TW, int K1, int S1, int K2>
 __global__ __launch_bounds__(256) void decoder_split_kernel(DecArgs a) {
     using G = DecSplit<TW, K1, S1, K2>;
@@ -96,17 +121,17 @@ __global__ __launch_bounds__(256) void decoder_split_kernel(DecArgs a) {
     const int q = threadIdx.x & 7, nl = threadIdx.x >> 3;
     const long n = (long)blockIdx.x * NODES + nl;
     const long nc = n < a.n_nodes ? n : a.n_nodes - 1;
-    const DecW w{a.w1, a.b1, a.w2, a.b2, a.u, a.dt, a.out};
-    decoder_split_node<TW, K1, S1, K2, false>(a.h + (size_t)nc * H, mid + (size_t)nl * 8 * LP, q, n < a.n_nodes, n, w, [] { __syncthreads(); });
+    decoder_split_node<TW, K1, S1, K2>(a.h + (size_t)nc * H, mid + (size_t)nl * 8 * LP, q, n < a.n_nodes, n, a);
 }
 
 // ----------------------------------------------------------------------------------------------
 // Decoder of the *2D solver classes (two solution components), experiments/models_gnn2D.py:79-88, 125-141:
 //   diff = Conv1d(8 -> 2, k2)( Swish( Conv1d(2 -> 8, k1, stride s1)( hd ) ) ),   hd = double_mlp(h)  [N, 2, 128]
 //   out  = unflatten(u) + cumsum(dt) * diff, flattened back to [N, 2*tw]
-// Eight lanes per node, lane c = intermediate channel c: it builds mid[c][:] from both input rows (the eight
-// lanes of a node read the same two 512-B rows: one L1 line fetch serves them), applies Swish, forms its
-// contribution to the 2*tw outputs, and the eight contributions are summed with three xor-shuffles.
+// Split by position like decoder_split_kernel: lane q builds the intermediate positions [q PP, (q + 1) PP) of all eight channels from
+// windows of BOTH input rows, the node's 8 x L1 intermediates meet in LDS, lane q forms OPL consecutive outputs of both components.
+// Summation order: an intermediate starts from its bias and adds the taps of input row 0, then of row 1, ascending; an output adds,
+// per channel, its taps ascending from 0, then the eight channel sums as a tree (pairs, pairs of pairs, halves), then the bias.
 // ----------------------------------------------------------------------------------------------
 struct Dec2Args {
     const float* hd;     // [N, 2, 128]
@@ -120,83 +145,6 @@ struct Dec2Args {
     float* out;          // [N, 2*tw]
 };
 
-template <int TW, int K1, int S1, int K2>
-__global__ __launch_bounds__(256) void decoder2d_kernel(Dec2Args a) {
-    constexpr int L1 = (H - K1) / S1 + 1;
-    static_assert(L1 - K2 + 1 == TW, "decoder geometry");
-    const int c = threadIdx.x & 7;
-    const long n = (long)blockIdx.x * 32 + (threadIdx.x >> 3);
-    const long nc = n < a.n_nodes ? n : a.n_nodes - 1;
-    float mid[L1];
-    const float bc = a.b1[c];
-#pragma unroll
-    for (int p = 0; p < L1; ++p) mid[p] = bc;
-#pragma unroll 1
-    for (int ci = 0; ci < 2; ++ci) {
-        float x[H];
-        const f32x4* hp = reinterpret_cast<const f32x4*>(a.hd + ((size_t)nc * 2 + ci) * H);
-#pragma unroll
-        for (int i = 0; i < H / 4; ++i) {
-            const f32x4 v = hp[i];
-            x[4 * i] = v[0]; x[4 * i + 1] = v[1]; x[4 * i + 2] = v[2]; x[4 * i + 3] = v[3];
-        }
-        float w[K1];
-#pragma unroll
-        for (int j = 0; j < K1; ++j) w[j] = a.w1[(c * 2 + ci) * K1 + j];
-#pragma unroll
-        for (int p = 0; p < L1; ++p) {
-            float s = mid[p];
-#pragma unroll
-            for (int j = 0; j < K1; ++j) s = fmaf(w[j], x[p * S1 + j], s);
-            mid[p] = s;
-        }
-    }
-#pragma unroll
-    for (int p = 0; p < L1; ++p) mid[p] = swishf(mid[p]);
-    float o[2 * TW];
-#pragma unroll
-    for (int co = 0; co < 2; ++co) {
-        float w[K2];
-#pragma unroll
-        for (int j = 0; j < K2; ++j) w[j] = a.w2[(co * 8 + c) * K2 + j];
-#pragma unroll
-        for (int t = 0; t < TW; ++t) {
-            float s = 0.f;
-#pragma unroll
-            for (int j = 0; j < K2; ++j) s = fmaf(w[j], mid[t + j], s);
-            o[co * TW + t] = s;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 2 * TW; ++i) {
-        float v = o[i];
-        v += __shfl_xor(v, 1);
-        v += __shfl_xor(v, 2);
-        v += __shfl_xor(v, 4);
-        o[i] = v;
-    }
-    if (n >= a.n_nodes) return;
-    const float b20 = a.b2[0], b21 = a.b2[1];
-    float tcum = 0.f;
-#pragma unroll
-    for (int t = 0; t < TW; ++t) {
-        tcum += a.dt;
-        // lane c writes the outputs whose flat index i = co*TW + t satisfies i % 8 == c
-#pragma unroll
-        for (int co = 0; co < 2; ++co) {
-            const int i = co * TW + t;
-            if ((i & 7) == c) a.out[(size_t)n * 2 * TW + i] = a.u[(size_t)n * 2 * TW + i] + tcum * (o[i] + (co ? b21 : b20));
-        }
-    }
-}
-
-// ----------------------------------------------------------------------------------------------
-// The *2D decoder split by position like decoder_split_kernel (eight lanes per node; decoder2d_kernel keeps a 128-value input row,
-// 38-59 intermediates and 2 tw partial outputs per lane).  Lane q builds the intermediate positions [q PP, (q + 1) PP) of all eight
-// channels from windows of BOTH input rows, the node's 8 x L1 intermediates meet in LDS, lane q forms OPL consecutive outputs of both
-// components.  Sums are formed exactly as decoder2d_kernel forms them -- per channel over the taps, the eight channel sums in the
-// order of its xor-shuffle tree, then the bias -- the same bits.
-// ----------------------------------------------------------------------------------------------
 template <int TW, int K1, int S1, int K2>
 __global__ __launch_bounds__(256) void decoder2d_split_kernel(Dec2Args a) {
     using G = DecSplit<TW, K1, S1, K2>;
@@ -269,7 +217,7 @@ __global__ __launch_bounds__(256) void decoder2d_split_kernel(Dec2Args a) {
         if (t0 + i < TW) {
 #pragma unroll
             for (int co = 0; co < 2; ++co) {
-                // the xor-shuffle tree of decoder2d_kernel: pairs, pairs of pairs, halves
+                // the eight channel sums as a tree: pairs, pairs of pairs, halves
                 const float s01 = sc[co][0][i] + sc[co][1][i], s23 = sc[co][2][i] + sc[co][3][i];
                 const float s45 = sc[co][4][i] + sc[co][5][i], s67 = sc[co][6][i] + sc[co][7][i];
                 const float v = (s01 + s23) + (s45 + s67);
@@ -284,59 +232,43 @@ __global__ __launch_bounds__(256) void decoder2d_split_kernel(Dec2Args a) {
 
 using namespace msmp;
 
+#define MSMP_DEC_SPLIT(KERNEL, TW_, K1_, S1_, K2_) do { using G_ = DecSplit<TW_, K1_, S1_, K2_>; \
+        hipLaunchKernelGGL((KERNEL<TW_, K1_, S1_, K2_>), dim3((unsigned)((n_nodes + G_::NODES - 1) / G_::NODES)), dim3(G_::NODES * 8), 0, st, a); } while (0)
+
 extern "C" int msmp_decoder2d_f32(const float* hd, const float* u, int64_t n_nodes, int tw, const float* w1, const float* b1,
                                   const float* w2, const float* b2, float dt, float* out, msmp_stream_t stream) {
     MSMP_REQUIRE(hd && u && w1 && b1 && w2 && b2 && out, MSMP_ERR_ARG, "msmp_decoder2d_f32: null pointer");
     MSMP_REQUIRE(n_nodes > 0 && n_nodes < (1L << 31), MSMP_ERR_ARG, "msmp_decoder2d_f32: bad n_nodes");
     Dec2Args a{hd, u, (long)n_nodes, w1, b1, w2, b2, dt, out};
-    const unsigned grid = (unsigned)((n_nodes + 31) / 32);
     hipStream_t st = (hipStream_t)stream;
     timing_begin(MSMP_K_DECODER, st);
-#define MSMP_DEC2_SPLIT(TW_, K1_, S1_, K2_) do { using G_ = DecSplit<TW_, K1_, S1_, K2_>; \
-        hipLaunchKernelGGL((decoder2d_split_kernel<TW_, K1_, S1_, K2_>), dim3((unsigned)((n_nodes + G_::NODES - 1) / G_::NODES)), dim3(G_::NODES * 8), 0, st, a); } while (0)
-    if (msmp_tune_get("decoder") && (tw == 25 || tw == 50)) {
-        if (tw == 25) MSMP_DEC2_SPLIT(25, 16, 3, 14); else MSMP_DEC2_SPLIT(50, 12, 2, 10);
-    } else
-#undef MSMP_DEC2_SPLIT_GUARD
     switch (tw) {   // experiments/models_gnn2D.py:79-88
-        case 25: hipLaunchKernelGGL((decoder2d_kernel<25, 16, 3, 14>), dim3(grid), dim3(256), 0, st, a); break;
-        case 50: hipLaunchKernelGGL((decoder2d_kernel<50, 12, 2, 10>), dim3(grid), dim3(256), 0, st, a); break;
+        case 25: MSMP_DEC_SPLIT(decoder2d_split_kernel, 25, 16, 3, 14); break;
+        case 50: MSMP_DEC_SPLIT(decoder2d_split_kernel, 50, 12, 2, 10); break;
         default:
             set_error("msmp_decoder2d_f32: time_window %d (the reference defines 25, 50)", tw);
             return MSMP_ERR_UNSUPPORTED;
     }
     timing_end(MSMP_K_DECODER, st);
-    return check_launch("decoder2d_kernel");
+    return check_launch("decoder2d_split_kernel");
 }
-
 
 extern "C" int msmp_decoder_f32(const float* h, const float* u, int64_t n_nodes, int tw, const float* w1, const float* b1,
                                 const float* w2, const float* b2, float dt, float* out, msmp_stream_t stream) {
     MSMP_REQUIRE(h && w1 && b1 && w2 && b2 && out, MSMP_ERR_ARG, "msmp_decoder_f32: null pointer");
     MSMP_REQUIRE(n_nodes > 0 && n_nodes < (1L << 31), MSMP_ERR_ARG, "msmp_decoder_f32: bad n_nodes");
     DecArgs a{h, u, (long)n_nodes, w1, b1, w2, b2, dt, out};
-    const unsigned grid = (unsigned)((n_nodes + 255) / 256);
     hipStream_t st = (hipStream_t)stream;
     timing_begin(MSMP_K_DECODER, st);
-#define MSMP_DEC_SPLIT(TW_, K1_, S1_, K2_) do { using G_ = DecSplit<TW_, K1_, S1_, K2_>; \
-        hipLaunchKernelGGL((decoder_split_kernel<TW_, K1_, S1_, K2_>), dim3((unsigned)((n_nodes + G_::NODES - 1) / G_::NODES)), dim3(G_::NODES * 8), 0, st, a); } while (0)
-    if (msmp_tune_get("decoder")) switch (tw) {   // experiments/models_gnn.py:210-224
-        case 20: MSMP_DEC_SPLIT(20, 15, 4, 10); break;
-        case 25: MSMP_DEC_SPLIT(25, 16, 3, 14); break;
-        case 50: MSMP_DEC_SPLIT(50, 12, 2, 10); break;
-        default:
-            set_error("msmp_decoder_f32: time_window %d (the reference defines 20, 25, 50)", tw);
-            return MSMP_ERR_UNSUPPORTED;
-    } else
-    switch (tw) {   // the one-lane-per-node edition (msmp_tune("decoder", 0))
-        case 20: hipLaunchKernelGGL((decoder_kernel<20, 15, 4, 10>), dim3(grid), dim3(256), 0, st, a); break;
-        case 25: hipLaunchKernelGGL((decoder_kernel<25, 16, 3, 14>), dim3(grid), dim3(256), 0, st, a); break;
-        case 50: hipLaunchKernelGGL((decoder_kernel<50, 12, 2, 10>), dim3(grid), dim3(256), 0, st, a); break;
+    switch (tw) {   // experiments/models_gnn.py:210-224
+        case 20: MSMP_DEC_SPLIT(decoder_split_kernel, 20, 15, 4, 10); break;
+        case 25: MSMP_DEC_SPLIT(decoder_split_kernel, 25, 16, 3, 14); break;
+        case 50: MSMP_DEC_SPLIT(decoder_split_kernel, 50, 12, 2, 10); break;
         default:
             set_error("msmp_decoder_f32: time_window %d (the reference defines 20, 25, 50)", tw);
             return MSMP_ERR_UNSUPPORTED;
     }
-#undef MSMP_DEC_SPLIT
     timing_end(MSMP_K_DECODER, st);
-    return check_launch("decoder_kernel");
+    return check_launch("decoder_split_kernel");
 }
+#undef MSMP_DEC_SPLIT

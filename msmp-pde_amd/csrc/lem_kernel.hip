@@ -871,8 +871,6 @@ extern "C" __attribute__((visibility("default"))) int msmp_debug_prof_lem(unsign
     return (int)hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_prof_lem), 16 * sizeof(unsigned long long));
 }
 #endif
-int g_lem_share = 1;     // msmp_tune("lem_share", k): k launches of this kind share the GPU (sub-batches on k streams): a launch plans for CUs / k
-int g_lem_tail = 1;      // msmp_tune("lem_tail", 0): every workgroup of the ws3 kernel takes three tiles (no round of one-tile workgroups)
 // Partition of n_nodes into three-tile workgroups [0, full) and one-tile workgroups behind them (lem_encoder_ws3_kernel).  Cost
 // model in rounds of one workgroup per CU: a three-tile workgroup 1, a one-tile workgroup 0.5 (measured at 2048 graphs: 203 vs 99 us per
 // round at T = 25); the one-tile round is taken only when it saves at least 0.3 of a round (small launches measured slower with it).
@@ -891,9 +889,9 @@ static unsigned lem_partition_for(int64_t n_nodes, int cus, int tail, int* full_
 static unsigned lem_partition(int64_t n_nodes, int* full_wgs) {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    cus = cus / (g_lem_share > 0 ? g_lem_share : 1);
+    cus = cus / msmp_tune_get("lem_share");     // k launches of this kind share the GPU (sub-batches on k streams): each plans for CUs / k
     if (cus < 1) cus = 1;
-    return lem_partition_for(n_nodes, cus, g_lem_tail, full_wgs);
+    return lem_partition_for(n_nodes, cus, msmp_tune_get("lem_tail"), full_wgs);
 }
 // (tests, no GPU needed) the partition of n_nodes for a device of `cus` CUs: grid size and the number of three-tile workgroups
 extern "C" __attribute__((visibility("default"))) int msmp_debug_lem_partition(int64_t n_nodes, int cus, int64_t* grid_out, int64_t* full_out) {

@@ -324,8 +324,6 @@ __global__ __launch_bounds__(64 * KT) void lem_wide_kernel(LemWideArgs a) {
 
 using namespace msmp;
 
-int g_lem_wide = 1;     // msmp_tune("lem_wide", 0): the host keeps the per-step GEMM + pointwise loop at widths other than 128
-
 static bool lem_wide_shape_ok(const char* who, int ninp, int width) {
     if (!wide_width_ok(who, width)) return false;
     if (ninp < 1 || ninp > LEM_MAX_INP) {

@@ -15,9 +15,7 @@
 //     one barrier per chunk; the packed blob stores chunks contiguously so staging is a flat copy.
 // k order inside a chunk is k = 8q + 4hh + m (q, m = 0..3): one 16-byte fragment load covers four
 // MFMA steps for both operands.  fp32 MFMA is an exact k-ordered fmaf chain (no reduced precision).
-#include <string.h>
 #include "mfma_tiles.h"
-#include "decoder_body.h"
 
 namespace msmp {
 
@@ -970,7 +968,6 @@ struct TailArgs {
     const float* scales[2];
     float* out;
     int* status;             // msmp_last_status word (or nullptr)
-    DecW dec;                // dec.w1 != nullptr: the 1-D decoder (time_window 25) runs as this launch's epilogue on the rows it wrote
 };
 
 // One update head, update_net_2 transposed: yT[T][r] = 2^s4 (W4 Swish(W3 [h ; agg ; vars] + b3) + b4)[channel 4 c + T]
@@ -1399,23 +1396,6 @@ __global__ __launch_bounds__(256, 2) void node_tail_split_kernel(TailArgs a) {
         }
     }
     PROF_MARK(4);
-    // Fused decoder (models_gnn.py:1371-1375 on the last pair's output): the graph's h' rows have just been stored by this
-    // workgroup; after the barrier (its release waits for the stores) they are read back past the L1 -- from the L2 they were written
-    // to, not from HBM -- by the position-split decoder, 32 nodes per pass, eight lanes per node, the per-node tables in the dead weight /
-    // row buffers (16 nodes each).  Same arithmetic as decoder_split_kernel: the same bits.
-    if (a.dec.w1) {
-        using G = DecSplit<25, 16, 3, 14>;
-        static_assert(16 * 8 * G::LP <= 2 * SPLIT_CHUNK_FLOATS && 16 * 8 * G::LP <= 2 * ROWBUF_FLOATS, "decoder tables must fit the dead buffers");
-        __syncthreads();
-        const int q = tid & 7, nl = tid >> 3;
-        float* mrow = (nl < 16 ? lds : rowbuf) + (nl & 15) * 8 * G::LP;
-        for (int p = 0; p < cnt; p += 32) {
-            const bool live = p + nl < cnt;
-            const long nn = live ? (long)n0 + p + nl : (long)n1 - 1;
-            decoder_split_node<25, 16, 3, 14, true>(a.out + (size_t)nn * H, mrow, q, live, nn, a.dec, [] { __syncthreads(); });
-            __syncthreads();
-        }
-    }
     PROF_FLUSH
 }
 
@@ -1423,15 +1403,8 @@ __global__ __launch_bounds__(256, 2) void node_tail_split_kernel(TailArgs a) {
 
 using namespace msmp;
 
-extern int g_lem_tail;
-extern int g_lem_share;
-extern int g_lem_wide;
-extern int g_wide_msg;
-extern int g_wide_tail;
-extern int g_wide_proj;
-// the sticky range status is the fp16-split path's: the exact-fp32 kernels have no range to leave (they run the data the split path could not)
-static int* split_status() { return msmp_tune_get("split") ? msmp::status_ptr() : nullptr; }
-static int g_split = 1;      // fp16-split matrix path (default); msmp_tune("split", 0) selects the fp32-MFMA kernels
+// The sticky range status (status_ptr) is the fp16-split path's: the exact-fp32 kernels have no range to leave (they run the data the
+// split path could not) and get nullptr.
 
 extern "C" int msmp_edge_mlp_f32(const float* h, const float* u, const float* pos, const float* vars,
                                  const int32_t* tgt, const int32_t* col, int64_t n_nodes, int64_t n_edges,
@@ -1443,7 +1416,7 @@ extern "C" int msmp_edge_mlp_f32(const float* h, const float* u, const float* po
     if (n_edges == 0) return MSMP_OK;
     const PackedLayout L = packed_layout(tw, nv);
     EdgeArgs a{h, u, pos, vars, tgt, col, nullptr, (long)n_edges, (long)n_nodes, 0, 0, tw, nv, L.nc1,
-               packed + L.w1, packed + L.w2, packed + L.w2s, packed + L.scales, packed + L.b1, packed + L.b2, nullptr, nullptr, msg_out, nullptr, split_status()};
+               packed + L.w1, packed + L.w2, packed + L.w2s, packed + L.scales, packed + L.b1, packed + L.b2, nullptr, nullptr, msg_out, nullptr, msmp_tune_get("split") ? status_ptr() : nullptr};
     constexpr int NB = 2;
     const unsigned grid = (unsigned)((n_edges + 128 * NB - 1) / (128 * NB));
     timing_begin(MSMP_K_EDGE_MLP, (hipStream_t)stream);
@@ -1461,7 +1434,7 @@ extern "C" int msmp_node_project_f32(const float* h, const float* u, const float
     ProjArgs a{h, u, pos, vars, (long)n_nodes, tw, nv, L.nc1, packed + L.w1, packed + L.b1, p_out, q_out};
     const unsigned grid = (unsigned)((n_nodes + 127) / 128);
     timing_begin(MSMP_K_NODE_PROJ, (hipStream_t)stream);
-    if (g_split) {
+    if (msmp_tune_get("split")) {
         ProjSplitArgs sa{a, packed + L.w1t, packed + L.scales};
         hipLaunchKernelGGL(node_proj_split_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, sa);
     } else
@@ -1470,58 +1443,7 @@ extern "C" int msmp_node_project_f32(const float* h, const float* u, const float
     return check_launch("node_proj_kernel");
 }
 
-static int g_edge_nb = 0;    // tuning override (msmp_tune): 0 = automatic, 1 / 2 = force the tile size of the factorised kernel
-
-static int g_pair = 1;       // gated pair: both heads' projection / message kernels in one launch each: 0 never, 1 up to PAIR_MAX_NODES nodes, 2 always
-constexpr int64_t PAIR_MAX_NODES = 65536;     // measured (E2, ms per rollout step, per-head vs paired): 256 graphs 1.33 / 1.14, 512: 2.06 / 1.95, 1024: 3.63 / 3.65, 2048: 6.95 / 7.07
-static int g_decoder = 1;     // 1-D decoder: 1 = eight lanes per node, split by position; 0 = one lane per node (decoder_kernel.hip)
-static int g_tile_arith = 1;  // ranged tiles: slot -> node arithmetically (tile_halo) instead of through the node list
-static int g_tile_align = 0;  // host layer: cut node tiles at graph boundaries also where tile_nodes does not divide the graph size (bitwise graph-order / sharding equivariance on knn graphs, ~11-20 % more tiles there)
-static int g_tile = 2;       // node tiles (tile_kernels.hip): 2 fold the projections into the message kernel, 1 staged P / Q rows, 0 off
-static int g_bwd_gemm = 1;   // layer backward: row GEMMs on rows_gemm_kernel (bf16x3 MFMA, fused epilogues); 0: rocblas_sgemm + separate passes
-static int g_dec_fuse = 0;   // host layer: the 1-D decoder as the epilogue of the last layer's node tail (msmp_mp_layer_decode_f32); measured, not the default
-static int g_tail = 1;       // fused node tail (msmp_node_tail_f32) inside msmp_mp_layer_f32; msmp_tune("tail", 0) chains the pieces
-int msmp_tune_get(const char* key) {
-    if (!strcmp(key, "split")) return g_split;
-    if (!strcmp(key, "tail")) return g_tail;
-    if (!strcmp(key, "bwd_gemm")) return g_bwd_gemm;
-    if (!strcmp(key, "pair")) return g_pair;
-    if (!strcmp(key, "tile")) return g_tile;
-    if (!strcmp(key, "tile_arith")) return g_tile_arith;
-    if (!strcmp(key, "tile_align")) return g_tile_align;
-    if (!strcmp(key, "decoder")) return g_decoder;
-    if (!strcmp(key, "dec_fuse")) return g_dec_fuse;
-    if (!strcmp(key, "lem_tail")) return g_lem_tail;
-    if (!strcmp(key, "lem_share")) return g_lem_share;
-    if (!strcmp(key, "lem_wide")) return g_lem_wide;
-    if (!strcmp(key, "wide_msg")) return g_wide_msg;
-    if (!strcmp(key, "wide_tail")) return g_wide_tail;
-    if (!strcmp(key, "wide_proj")) return g_wide_proj;
-    return 0;
-}
-
-extern "C" int msmp_tune_query(const char* key) { return key ? msmp_tune_get(key) : 0; }
-
-extern "C" int msmp_tune(const char* key, int value) {
-    if (key && !strcmp(key, "tail")) { g_tail = value; return MSMP_OK; }
-    if (key && !strcmp(key, "bwd_gemm")) { g_bwd_gemm = value; return MSMP_OK; }
-    if (key && !strcmp(key, "pair")) { g_pair = value; return MSMP_OK; }
-    if (key && !strcmp(key, "tile")) { g_tile = value; return MSMP_OK; }
-    if (key && !strcmp(key, "tile_arith")) { g_tile_arith = value; return MSMP_OK; }
-    if (key && !strcmp(key, "tile_align")) { g_tile_align = value; return MSMP_OK; }
-    if (key && !strcmp(key, "decoder")) { g_decoder = value != 0; return MSMP_OK; }
-    if (key && !strcmp(key, "dec_fuse")) { g_dec_fuse = value != 0; return MSMP_OK; }
-    if (key && !strcmp(key, "lem_tail")) { g_lem_tail = value != 0; return MSMP_OK; }
-    if (key && !strcmp(key, "lem_share") && value >= 1 && value <= 16) { g_lem_share = value; return MSMP_OK; }
-    if (key && !strcmp(key, "lem_wide")) { g_lem_wide = value != 0; return MSMP_OK; }
-    if (key && !strcmp(key, "wide_msg")) { g_wide_msg = value != 0; return MSMP_OK; }
-    if (key && !strcmp(key, "wide_tail")) { g_wide_tail = value != 0; return MSMP_OK; }
-    if (key && !strcmp(key, "wide_proj")) { g_wide_proj = value != 0; return MSMP_OK; }
-    if (key && !strcmp(key, "edge_nb")) { g_edge_nb = value; return MSMP_OK; }
-    if (key && !strcmp(key, "split")) { g_split = value; return MSMP_OK; }
-    msmp::set_error("msmp_tune: unknown key");
-    return MSMP_ERR_ARG;
-}
+constexpr int64_t PAIR_MAX_NODES = 65536;     // "pair" 1, measured (E2, ms per rollout step, per-head vs paired): 256 graphs 1.33 / 1.14, 512: 2.06 / 1.95, 1024: 3.63 / 3.65, 2048: 6.95 / 7.07
 
 static int edge_aggregate(const float* h, const float* u, const float* pos, const float* vars, const float* P, const float* Q,
                           const int32_t* rowptr, const int32_t* col, const int32_t* tgt, int64_t n_nodes, int64_t n_edges,
@@ -1540,15 +1462,16 @@ static int edge_aggregate(const float* h, const float* u, const float* pos, cons
                  "%s: max in-degree %d > 256 (use msmp_edge_mlp_f32 + msmp_scatter_mean_f32)", who, max_in_degree);
     // Tile = 128 edges (NB = 1: <= 256 registers, two workgroups per CU so one's gathers / Swish / reduce overlap the
     // other's MFMAs) when the factorised form is used and the degrees allow, else 256 edges (NB = 2).
-    const int edges_per_tile = (P && max_in_degree <= 128 && g_edge_nb != 2) ? 128 : 256;
+    const bool split = msmp_tune_get("split") != 0;
+    const int edges_per_tile = (P && max_in_degree <= 128 && msmp_tune_get("edge_nb") != 2) ? 128 : 256;
     const PackedLayout L = packed_layout(tw, nv);
     int tile_nodes = max_in_degree > 0 ? edges_per_tile / max_in_degree : edges_per_tile;
     if (tile_nodes > 256) tile_nodes = 256;      // keeps the per-tile node loop short when degrees are tiny
     EdgeArgs a{h, u, pos, vars, tgt, col, rowptr, (long)n_edges, (long)n_nodes, tile_nodes, 0, tw, nv, L.nc1,
-               packed + L.w1, packed + L.w2, packed + L.w2s, packed + L.scales, packed + L.b1, packed + L.b2, P, Q, nullptr, agg_out, split_status()};
+               packed + L.w1, packed + L.w2, packed + L.w2s, packed + L.scales, packed + L.b1, packed + L.b2, P, Q, nullptr, agg_out, split ? status_ptr() : nullptr};
     const unsigned grid = (unsigned)((n_nodes + tile_nodes - 1) / tile_nodes);
     timing_begin(MSMP_K_EDGE_MLP, (hipStream_t)stream);
-    if (P && edges_per_tile == 128 && g_split) hipLaunchKernelGGL((edge_mlp_kernel_occ2<1, true, true, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+    if (P && edges_per_tile == 128 && split) hipLaunchKernelGGL((edge_mlp_kernel_occ2<1, true, true, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
     else if (P && edges_per_tile == 128) hipLaunchKernelGGL((edge_mlp_kernel<1, true, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
     else if (P) hipLaunchKernelGGL((edge_mlp_kernel<2, true, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL((edge_mlp_kernel<2, true, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
@@ -1563,8 +1486,9 @@ int msmp_pair_project_aggregate(const float* h, const float* u, const float* pos
                                 const int32_t* col, const int32_t* tgt, int64_t n_nodes, int64_t n_edges, int max_in_degree, int tw,
                                 int nv, const float* packed_a, const float* packed_b, float* p_a, float* q_a, float* p_b, float* q_b,
                                 float* agg_a, float* agg_b, msmp_stream_t stream) {
-    if (!g_pair || (g_pair == 1 && n_nodes > PAIR_MAX_NODES)) return MSMP_ERR_UNSUPPORTED;
-    if (!g_split || g_edge_nb == 2) return MSMP_ERR_UNSUPPORTED;
+    const int pair = msmp_tune_get("pair");
+    if (!pair || (pair == 1 && n_nodes > PAIR_MAX_NODES)) return MSMP_ERR_UNSUPPORTED;
+    if (!msmp_tune_get("split") || msmp_tune_get("edge_nb") == 2) return MSMP_ERR_UNSUPPORTED;
     if (n_edges <= 0 || max_in_degree <= 0 || max_in_degree > 128 || n_edges >= (1L << 31) || n_nodes >= (1L << 31)) return MSMP_ERR_UNSUPPORTED;
     const PackedLayout L = packed_layout(tw, nv);
     hipStream_t st = (hipStream_t)stream;
@@ -1585,7 +1509,7 @@ int msmp_pair_project_aggregate(const float* h, const float* u, const float* pos
     for (int i = 0; i < 2; ++i)
         ea.head[i] = EdgeArgs{nullptr, nullptr, nullptr, nullptr, tgt, col, rowptr, (long)n_edges, (long)n_nodes, tile_nodes, 0, tw, nv, L.nc1,
                               packed[i] + L.w1, packed[i] + L.w2, packed[i] + L.w2s, packed[i] + L.scales, packed[i] + L.b1,
-                              packed[i] + L.b2, pp[i], qq[i], nullptr, agg[i], split_status()};
+                              packed[i] + L.b2, pp[i], qq[i], nullptr, agg[i], status_ptr()};
     timing_begin(MSMP_K_EDGE_MLP, st);
     hipLaunchKernelGGL(edge_mlp_pair_kernel_occ2, dim3((unsigned)((n_nodes + tile_nodes - 1) / tile_nodes), 2), dim3(256), 0, st, ea);
     timing_end(MSMP_K_EDGE_MLP, st);
@@ -1620,14 +1544,6 @@ extern "C" int msmp_node_tail_f32(const float* h, const float* agg_main, const f
                                   const int32_t* graph_ptr, int64_t n_nodes, int64_t n_graphs, int max_graph_nodes, int nv,
                                   const float* packed_main, const float* packed_gate, int mode, float eps, float* out,
                                   msmp_stream_t stream) {
-    return msmp_node_tail_impl(h, agg_main, agg_gate, vars, graph_ptr, n_nodes, n_graphs, max_graph_nodes, nv, packed_main, packed_gate, mode,
-                               eps, out, nullptr, stream);
-}
-
-// The same with the 1-D decoder as the launch's epilogue (library-internal: msmp_mp_layer_decode_f32)
-int msmp_node_tail_impl(const float* h, const float* agg_main, const float* agg_gate, const float* vars, const int32_t* graph_ptr,
-                        int64_t n_nodes, int64_t n_graphs, int max_graph_nodes, int nv, const float* packed_main, const float* packed_gate,
-                        int mode, float eps, float* out, const msmp_decoder_t* dec, msmp_stream_t stream) {
     MSMP_REQUIRE(h && agg_main && vars && graph_ptr && packed_main && out, MSMP_ERR_ARG, "msmp_node_tail_f32: null pointer");
     MSMP_REQUIRE((agg_gate != nullptr) == (packed_gate != nullptr), MSMP_ERR_ARG, "msmp_node_tail_f32: give both gate arguments or none");
     MSMP_REQUIRE(n_nodes > 0 && n_graphs > 0 && n_graphs < (1L << 31) && nv >= 1 && nv <= MSMP_MAX_VARS, MSMP_ERR_ARG,
@@ -1637,17 +1553,12 @@ int msmp_node_tail_impl(const float* h, const float* agg_main, const float* agg_
     MSMP_REQUIRE(out != h, MSMP_ERR_ARG, "msmp_node_tail_f32: out may not alias h");
     MSMP_REQUIRE(max_graph_nodes > 0 && max_graph_nodes <= 128, MSMP_ERR_UNSUPPORTED,
                  "msmp_node_tail_f32: graphs of up to 128 nodes (got max_graph_nodes=%d); use the piecewise entry points", max_graph_nodes);
-    MSMP_REQUIRE(g_split, MSMP_ERR_UNSUPPORTED, "msmp_node_tail_f32: only on the fp16-split matrix path");
+    MSMP_REQUIRE(msmp_tune_get("split"), MSMP_ERR_UNSUPPORTED, "msmp_node_tail_f32: only on the fp16-split matrix path");
     const PackedLayout L = packed_layout(1, nv);   // w3/w4/b3/b4/w3v/w3s/scales offsets do not depend on tw
     const float* pg = packed_gate ? packed_gate : packed_main;
     TailArgs a{h, {agg_main, agg_gate}, vars, graph_ptr, nv, mode, eps,
                {packed_main + L.b3, pg + L.b3}, {packed_main + L.b4, pg + L.b4}, {packed_main + L.w3vh, pg + L.w3vh},
-               {packed_main + L.w3s, pg + L.w3s}, {packed_main + L.w4t, pg + L.w4t}, {packed_main + L.scales, pg + L.scales}, out, split_status(), DecW{}};
-    if (dec) {
-        MSMP_REQUIRE(dec->w1 && dec->b1 && dec->w2 && dec->b2 && dec->out, MSMP_ERR_ARG, "msmp_mp_layer_decode_f32: null pointer in the decoder description");
-        MSMP_REQUIRE(dec->time_window == 25, MSMP_ERR_UNSUPPORTED, "msmp_mp_layer_decode_f32: the fused decoder is built for time_window 25 (got %d)", dec->time_window);
-        a.dec = DecW{dec->w1, dec->b1, dec->w2, dec->b2, dec->u, dec->dt, dec->out};
-    }
+               {packed_main + L.w3s, pg + L.w3s}, {packed_main + L.w4t, pg + L.w4t}, {packed_main + L.scales, pg + L.scales}, out, status_ptr()};
     timing_begin(MSMP_K_NODE_UPDATE, (hipStream_t)stream);
     if (packed_gate) hipLaunchKernelGGL(node_tail_split_kernel<true>, dim3((unsigned)n_graphs), dim3(256), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(node_tail_split_kernel<false>, dim3((unsigned)n_graphs), dim3(256), 0, (hipStream_t)stream, a);
@@ -1667,7 +1578,7 @@ extern "C" int msmp_node_update_f32(const float* h, const float* agg, const floa
     constexpr int NB = 1;
     const unsigned grid = (unsigned)((n_nodes + 128 * NB - 1) / (128 * NB));
     timing_begin(MSMP_K_NODE_UPDATE, (hipStream_t)stream);
-    if (g_split) {
+    if (msmp_tune_get("split")) {
         NodeSplitArgs sa{a, packed + L.w3s, packed + L.scales};
         hipLaunchKernelGGL(node_update_split_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, sa);
     } else

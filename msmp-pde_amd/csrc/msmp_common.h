@@ -5,20 +5,16 @@
 #include <stdio.h>
 #include "msmp_pde.h"
 
-int msmp_tune_get(const char* key);
+int msmp_tune_get(const char* key);     // aux_kernels.hip: current value of a msmp_tune switch ("split", "tail", ...; 0 for an unknown key); library-internal
 int msmp_pair_project_aggregate(const float* h, const float* u, const float* pos, const float* vars, const int32_t* rowptr,
                                 const int32_t* col, const int32_t* tgt, int64_t n_nodes, int64_t n_edges, int max_in_degree, int tw,
                                 int nv, const float* packed_a, const float* packed_b, float* p_a, float* q_a, float* p_b, float* q_b,
                                 float* agg_a, float* agg_b, msmp_stream_t stream);   // mlp_kernels.hip, library-internal
-    // current value of a msmp_tune switch ("split", "tail"); library-internal
 int msmp_edge_aggregate_tiled_pair(const float* h, const float* u, const float* pos, const float* vars, const float* feat, const int32_t* rowptr,
                                    const msmp_tiles_t* tiles, int64_t n_nodes, int64_t n_edges, int tw, int nv, const float* packed_a,
                                    const float* packed_b, float* agg_a, float* agg_b, msmp_stream_t stream);   // tile_kernels.hip
 
-bool msmp_tiles_ok(const msmp_tiles_t* t, int64_t n_nodes);
-int msmp_node_tail_impl(const float* h, const float* agg_main, const float* agg_gate, const float* vars, const int32_t* graph_ptr,
-                        int64_t n_nodes, int64_t n_graphs, int max_graph_nodes, int nv, const float* packed_main, const float* packed_gate,
-                        int mode, float eps, float* out, const msmp_decoder_t* dec, msmp_stream_t stream);       // mlp_kernels.hip    // tile_kernels.hip: geometry of a caller-supplied tile descriptor
+bool msmp_tiles_ok(const msmp_tiles_t* t, int64_t n_nodes);     // tile_kernels.hip: geometry of a caller-supplied tile descriptor
 
 namespace msmp {
 

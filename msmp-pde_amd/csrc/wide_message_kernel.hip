@@ -275,8 +275,6 @@ __global__ __launch_bounds__(64 * KT, 2) void wide_message_kernel(WideMsgArgs a)
 
 using namespace msmp;
 
-int g_wide_msg = 1;     // msmp_tune("wide_msg", 0): the host layer keeps gather + row GEMM + scatter at widths other than 128
-
 extern "C" int64_t msmp_packed_wide_msg_floats(int width) {
     if (!wide_width_ok("msmp_packed_wide_msg_floats", width)) return 0;
     return wide_msg_layout((width + 31) / 32).total;

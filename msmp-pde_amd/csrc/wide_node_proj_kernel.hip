@@ -284,7 +284,6 @@ using namespace msmp;
 
 // msmp_tune("wide_proj", 1): the host layer takes this kernel at widths other than 128; 0 (default): the concatenation and two msmp_linear_f32
 // per head.  It ships at 0 until the per-step A/B and the full-depth error of DESIGN.md 4.21 are measured on the MI355X.
-int g_wide_proj = 0;
 
 static bool wide_proj_shape_ok(const char* who, int tw, int nv) {
     if (tw < 1 || nv < 1 || nv > MSMP_MAX_VARS) {

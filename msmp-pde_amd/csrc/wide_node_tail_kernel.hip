@@ -355,7 +355,6 @@ using namespace msmp;
 // msmp_tune("wide_tail", 1): the host layer takes this kernel at widths other than 128; 0 (default): concatenation + two row GEMMs +
 // msmp_wide_norm_blend_f32.  Faster by 22-25 % per step, but at full depth (6 gated pairs, untrained weights) the fp16-split arithmetic of
 // the node half misses the bar of test_full_depth_vs_oracle that the bf16x3 row GEMMs meet (profiles/r10a_glu_wide_node_tail.md)
-int g_wide_tail = 0;
 
 static bool wide_tail_nv_ok(const char* who, int nv) {
     if (nv < 0 || nv > MSMP_MAX_VARS) {

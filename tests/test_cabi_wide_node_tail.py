@@ -26,7 +26,7 @@ def test_header_declares_and_library_exports_the_entry(L):
     for name in NAMES:
         assert re.search(r'\b' + name + r'\s*\(', header), name
         assert getattr(L, name) is not None
-    assert re.search(r'#define\s+MSMP_ABI_VERSION\s+400\b', header) and L.msmp_version() == 400
+    assert re.search(r'#define\s+MSMP_ABI_VERSION\s+410\b', header) and L.msmp_version() == 410
     assert '"wide_tail"' in header
 
 

@@ -63,8 +63,59 @@ def test_argument_errors_and_retired_tune_keys_are_reported_not_thrown(mp):
     # knobs: known keys are accepted, unknown ones rejected with a message ("lem" / "lem_nodes" are retired: "split" selects the LEM kernel)
     for key in (b'split', b'edge_nb', b'tail', b'pair', b'tile'):
         assert L.msmp_tune(key, {b'split': 1, b'tail': 1, b'pair': 1, b'tile': 2}.get(key, 0)) == 0, key
-    for key in (b'no_such_knob', b'lem', b'lem_nodes'):
+    for key in (b'no_such_knob', b'lem', b'lem_nodes', b'dec_fuse', b'decoder'):
         assert L.msmp_tune(key, 1) != 0 and b'unknown key' in L.msmp_last_error(), key
+        assert L.msmp_tune_query(key) == 0, key
+    assert L.msmp_tune(None, 1) == -1 and b'unknown key' in L.msmp_last_error() and L.msmp_tune_query(None) == 0
+
+
+def _documented_knobs():
+    """{key: default} of the knob list in include/msmp_pde.h: an entry starts with its quoted key and names its default either as
+    `N (default ...` or as `(default N ...`."""
+    hdr = open(os.path.join(ROOT, 'include', 'msmp_pde.h')).read()
+    text = hdr[hdr.index('/* Knobs for A/B measurements'):hdr.index('int msmp_tune(const char* key, int value);')]
+    entries = re.split(r'\n \*   (?=")', text)[1:]
+    knobs = {}
+    for e in entries:
+        key = re.match(r'"([a-z_]+)"', e).group(1)
+        m = re.search(r'(-?\d+) \(default\b|\(default (-?\d+)\b', e)
+        assert m, f'the entry of "{key}" does not name its default'
+        knobs[key.encode()] = int(m.group(1) or m.group(2))
+    return knobs
+
+
+def test_tune_table_matches_the_documented_knobs(mp):
+    """The switch table of the library and the knob list of the header name the same defaults, and every documented key can be set
+    and queried: a fresh library (a process of its own: nothing has touched its switches) reports the documented default, a value
+    set is the value queried (as 0 / 1 for the on/off keys), and "lem_share" refuses values outside 1 .. 16 with a message that
+    says so, leaving the value as it was.  No device work."""
+    import json
+    import subprocess
+    knobs = _documented_knobs()
+    on_off = {b'lem_tail', b'lem_wide', b'wide_msg', b'wide_tail', b'wide_proj'}       # stored as value != 0
+    assert len(knobs) >= 14 and on_off < set(knobs) and {b'split', b'edge_nb', b'tile_align', b'lem_share'} < set(knobs), sorted(knobs)
+    child = ('import ctypes, json, sys; L = ctypes.CDLL(sys.argv[1]); '
+             'print(json.dumps({k: L.msmp_tune_query(k.encode()) for k in sys.argv[2:]}))')
+    r = subprocess.run([sys.executable, '-c', child, mp.LIB_PATH] + [k.decode() for k in knobs], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    fresh = json.loads(r.stdout.strip().splitlines()[-1])
+    assert fresh == {k.decode(): v for k, v in knobs.items()}
+    L = mp.lib()
+    for key, default in knobs.items():
+        try:
+            for value in ((1, 2, 16) if key == b'lem_share' else (0, 1, 2, 5)):
+                assert L.msmp_tune(key, value) == 0, (key, value, L.msmp_last_error())
+                assert L.msmp_tune_query(key) == (int(value != 0) if key in on_off else value), (key, value)
+        finally:
+            L.msmp_tune(key, default)
+        assert L.msmp_tune_query(key) == default, key
+    assert L.msmp_tune(b'lem_share', 3) == 0
+    try:
+        for bad in (0, 17):
+            assert L.msmp_tune(b'lem_share', bad) == -1 and b'out of range' in L.msmp_last_error() and b'unknown key' not in L.msmp_last_error(), bad
+            assert L.msmp_tune_query(b'lem_share') == 3, bad
+    finally:
+        L.msmp_tune(b'lem_share', 1)
 
 
 @pytest.mark.parametrize('exp', ['E2', 'WE3', 'RPU', 'MSWG3'])
