@@ -1,5 +1,7 @@
-"""Shared helpers for the tests: golden loading, synthetic E2-shaped batches (no reference needed) and what the tests of the
-width-generic (hidden width != 128) path share."""
+"""Shared helpers for the tests: golden loading, synthetic E2-shaped batches (no reference needed), what the tests of the
+width-generic (hidden width != 128) path share, and what the route tests of the 128-wide layer entry point need (tune-switch
+and launch-count contexts, banded batches)."""
+import contextlib
 import os
 from types import SimpleNamespace
 
@@ -302,3 +304,76 @@ def counted(mp, monkeypatch, name):
         return real(*a)
     monkeypatch.setattr(L, name, entry)
     return calls
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Shared by the route tests of msmp_mp_layer_f32 (test_gpu_layer_routes.py) and the tiled-kernel tests (test_gpu_kernels.py).
+# ---------------------------------------------------------------------------------------------------------------------------
+@contextlib.contextmanager
+def tuned(L, **switches):
+    """msmp_tune keys set for the body of the `with`, then back at what msmp_tune_query returned before -- also when the body
+    raises.  The keyword DENSE_MESSAGE sets msmp_pde_amd.layers.DENSE_MESSAGE instead (restored in any case)."""
+    from msmp_pde_amd import layers
+    dense_before = layers.DENSE_MESSAGE
+    keys = {k: k.encode() for k in switches if k != 'DENSE_MESSAGE'}
+    before = {k: L.msmp_tune_query(b) for k, b in keys.items()}
+    try:
+        for k, b in keys.items():
+            assert L.msmp_tune(b, int(switches[k])) == 0, (k, switches[k], L.msmp_last_error())
+        if 'DENSE_MESSAGE' in switches:
+            layers.DENSE_MESSAGE = bool(switches['DENSE_MESSAGE'])
+        yield
+    finally:
+        layers.DENSE_MESSAGE = dense_before
+        for k, b in keys.items():
+            L.msmp_tune(b, before[k])
+
+
+TIMING_FAMILIES = ('EDGE_MLP', 'SCATTER_MEAN', 'NODE_UPDATE', 'NORM', 'LEM', 'NODE_PROJ', 'DECODER')      # MSMP_K_* of include/msmp_pde.h, in order
+
+
+@contextlib.contextmanager
+def launch_counts(L):
+    """{family: launches} of the library's own launch counters (msmp_timing_*) over the body of the `with`; the dict is filled on
+    exit (msmp_timing_read waits for the recorded events).  Every family is enabled and zeroed on entry, everything disabled and
+    zeroed again on exit.  This is the witness of which kernels an entry point chained: no monkeypatching, no look at code objects."""
+    from msmp_pde_amd import _lib
+    counts = {}
+    assert L.msmp_timing_enable((1 << len(TIMING_FAMILIES)) - 1) == 0 and L.msmp_timing_reset() == 0
+    try:
+        yield counts
+        for k, family in enumerate(TIMING_FAMILIES):
+            counts[family] = _lib.timing_read(k)[0]
+    finally:
+        L.msmp_timing_enable(0)
+        L.msmp_timing_reset()
+
+
+def banded_batch(sizes, reach):
+    """Banded chains of different lengths: every node is connected to its neighbours within `reach` inside its own graph.
+    (edge_index [2, E] int64 numpy: ascending target, then ascending source; batch [N] int64)."""
+    d = np.array([k for k in range(-reach, reach + 1) if k], dtype=np.int64)
+    src, tgt, off = [], [], 0
+    for m in sizes:
+        i = np.arange(m, dtype=np.int64)[:, None]
+        s_ = i + d[None, :]
+        ok = (s_ >= 0) & (s_ < m)
+        src.append((s_ + off)[ok]); tgt.append(np.broadcast_to(i + off, s_.shape)[ok])
+        off += m
+    ei = np.stack([np.concatenate(src), np.concatenate(tgt)]) if sizes else np.zeros((2, 0), dtype=np.int64)
+    return ei, np.repeat(np.arange(len(sizes), dtype=np.int64), sizes)
+
+
+def hub_batch(sizes, reach, graph, deg):
+    """banded_batch with ONE target rewired: the middle node of graph `graph` gets `deg` in-edges from the other nodes of its own
+    graph -- distinct sources while deg < sizes[graph], else the sources repeat round-robin (multi-edges: the CSR keeps them and a
+    mean counts them).  (edge_index sorted by target, batch, hub node)"""
+    ei, batch = banded_batch(sizes, reach)
+    m, start = sizes[graph], int(sum(sizes[:graph]))
+    hub = start + m // 2
+    others = np.array([start + j for j in range(m) if start + j != hub], dtype=np.int64)
+    keep = ei[1] != hub
+    src = np.concatenate([ei[0][keep], others[np.arange(deg) % len(others)]])
+    tgt = np.concatenate([ei[1][keep], np.full(deg, hub, dtype=np.int64)])
+    order = np.argsort(tgt, kind='stable')
+    return np.stack([src[order], tgt[order]]), batch, hub

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from oracle import msmp_oracle as O
-from helpers import load, sd_of, graph_of
+from helpers import load, sd_of, graph_of, banded_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -905,16 +905,9 @@ def test_tiled_message_kernel_on_batches_of_unequal_graphs(mp, sizes, reach):
     from msmp_pde_amd._lib import check, ptr, current_stream
     from msmp_pde_amd.graph import GraphStructure
     L = mp.lib()
-    src, tgt, batch, off = [], [], [], 0
-    for g, m in enumerate(sizes):
-        for i in range(m):
-            for d in range(-reach, reach + 1):
-                if d and 0 <= i + d < m:
-                    src.append(off + i + d); tgt.append(off + i)
-        batch += [g] * m
-        off += m
-    n = off
-    ei = torch.tensor([src, tgt], dtype=torch.int64).cuda()
+    ei, batch = banded_batch(sizes, reach)
+    n = len(batch)
+    ei = torch.tensor(ei, dtype=torch.int64).cuda()
     gs = GraphStructure(ei, torch.tensor(batch).cuda(), n)
     same_size = len(set(sizes)) == 1
     assert (gs.period() is not None) == (same_size and len(sizes) > 1)
