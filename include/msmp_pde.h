@@ -106,6 +106,10 @@ int msmp_last_status(int* flags_out, int reset);
  *             a gated pair) as one msmp_wide_node_proj_f32 launch; 0 (default): a concatenation [h | u | pos | vars] and two msmp_linear_f32 per head
  *             (the entry itself does not read the key).  The host takes the fused launch only while "wide_msg", "split" and "lem_wide" are 1
  *             as well, so each of those keeps selecting the path it selected before this kernel.
+ *   "wide_dec" 1 (default): the host's no-grad forward of the GLU classes ends in one msmp_decoder_gated_f32 / msmp_decoder2d_gated_f32
+ *             launch (2-D: after double_mlp as one msmp_linear_f32); 0: the decoder's PyTorch ops (the entries themselves do not read the
+ *             key; any value other than 0 selects the launch).  The host takes the launch only while "wide_msg", "split" and "lem_wide"
+ *             are 1 as well, so each of those keeps selecting the path it selected before these kernels.
  *   "tile_arith" 1 (default): ranged tiles take their node rows by arithmetic on tile_halo; 0: always through the node list.
  *   "tile_align" 0 (default): the host cuts the node tiles of a batch of identical graphs at graph boundaries only where tile_nodes divides
  *             the graph size; 1: also where it does not (bitwise graph-order / sharding equivariance on knn graphs, 11-20 % more tiles
@@ -355,6 +359,28 @@ int msmp_decoder_f32(const float* h, const float* u, int64_t n_nodes, int tw, co
 int msmp_decoder2d_f32(const float* hd, const float* u, int64_t n_nodes, int tw, const float* w1,
                        const float* b1, const float* w2, const float* b2, float dt, float* out,
                        msmp_stream_t stream);
+
+/* Gated CNN decoder of the GLU classes (hidden width 164, time_window 25), the two networks and the gated Euler update in one launch.
+ * 1-D, experiments/models_gnn.py:1455-1456 (output_mlp_gate / output_mlp_diff) and :1514-1521:
+ *   scale = Conv1d(8,1,15)(Swish(Conv1d(1,8,6,stride 2)(h[:, None, :82]))),  diff = the same of output_mlp_diff on h[:, None, 82:],
+ *   out = (1 - scale) * u[:, -1:] + cumsum(dt) * (scale * diff)              (no sigmoid on scale, as in the reference).
+ * h: rows of `width` floats at a row stride of ld floats (ld >= width; no alignment beyond that of a float); u, out [N, tw].
+ * gate_* / diff_*: w1 [8,1,6], b1 [8], w2 [1,8,15], b2 [1] of the two networks in the reference's Conv1d layouts.
+ * Any (width, tw) other than (164, 25) returns MSMP_ERR_UNSUPPORTED before anything is launched (the reference defines no other);
+ * null pointers, n_nodes outside 1 .. 2^31 - 1 and ld < width return MSMP_ERR_ARG.  Plain fp32 arithmetic: no range status. */
+int msmp_decoder_gated_f32(const float* h, int ld, const float* u, int64_t n_nodes, int width, int tw, const float* gate_w1,
+                           const float* gate_b1, const float* gate_w2, const float* gate_b2, const float* diff_w1, const float* diff_b1,
+                           const float* diff_w2, const float* diff_b2, float dt, float* out, msmp_stream_t stream);
+
+/* The same for the 2-D GLU class, experiments/models_gnn2D.py:1291-1298 and :1355-1366, after double_mlp:
+ *   scale = Conv1d(8,2,15)(Swish(Conv1d(2,8,6,stride 2)(hd[:, :, :82]))),  diff = the same of output_mlp_diff on hd[:, :, 82:],
+ *   out = (1 - scale) * unflatten(u) + cumsum(dt) * scale * diff, flattened back to [N, 2*tw]   (every column of u).
+ * hd: per node two component rows of `width` floats, component 1 `width` floats after component 0, nodes ld floats apart
+ * (ld >= 2 * width: msmp_linear_f32 writes double_mlp at ld = 384 and the decoder reads it in place); u, out [N, 2*tw] (component-major).
+ * gate_* / diff_*: w1 [8,2,6], b1 [8], w2 [2,8,15], b2 [2].  Refusals as above, with ld < 2 * width. */
+int msmp_decoder2d_gated_f32(const float* hd, int ld, const float* u, int64_t n_nodes, int width, int tw, const float* gate_w1,
+                             const float* gate_b1, const float* gate_w2, const float* gate_b2, const float* diff_w1, const float* diff_b1,
+                             const float* diff_w2, const float* diff_b2, float dt, float* out, msmp_stream_t stream);
 
 /* `double_mlp` of the *2D solver classes, experiments/models_gnn2D.py:66-70 (nn.Linear(128, 256) + Swish; the Unflatten is a view):
  * out [rows, n_out] = Swish(x [rows, k] w^T + bias), w [n_out, k] in nn.Linear's layout; n_out a multiple of 128, k a multiple of 4 up to 288.

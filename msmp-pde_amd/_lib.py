@@ -65,6 +65,8 @@ SIGNATURES = {
     'msmp_lem_encoder_f32': (c_int, [c_void_p, c_int64, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p]),
     'msmp_decoder_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
     'msmp_decoder2d_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
+    'msmp_decoder_gated_f32': (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_int] + [c_void_p] * 8 + [c_float, c_void_p, c_void_p]),
+    'msmp_decoder2d_gated_f32': (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_int] + [c_void_p] * 8 + [c_float, c_void_p, c_void_p]),
     'msmp_node_tail_f32': (c_int, [c_void_p] * 5 + [c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p]),
     'msmp_lem_encoder_nodes_f32': (c_int, [c_void_p] * 5 + [c_int64, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p]),
     'msmp_lem_saved_floats': (c_int64, [c_int64, c_int]),

@@ -10,9 +10,9 @@
 
 namespace msmp {
 
-template <int TW, int K1, int S1, int K2>
+template <int TW, int K1, int S1, int K2, int R = H>                // R: length of the row a network reads (the gated decoders: half a 164-wide row)
 struct DecSplit {
-    static constexpr int L1 = (H - K1) / S1 + 1;
+    static constexpr int L1 = (R - K1) / S1 + 1;
     static constexpr int PP = (L1 + 7) / 8;                          // intermediate positions per lane
     static constexpr int XW = (PP - 1) * S1 + K1;                    // row values a lane needs
     static constexpr int OPL = TW > 32 ? 8 : 4;                      // consecutive outputs per lane (multiple of 4: aligned 16-byte LDS reads)
@@ -228,6 +228,186 @@ __global__ __launch_bounds__(256) void decoder2d_split_kernel(Dec2Args a) {
     }
 }
 
+// ----------------------------------------------------------------------------------------------
+// Gated CNN decoder of the GLU classes (hidden width 164): two networks of the same geometry, `gate` on the first 82 values of a row and
+// `diff` on the last 82,  Conv1d(C -> 8, 6, stride 2) -> Swish -> Conv1d(8 -> C, 15)  each (L1 = 39 intermediate positions, 25 outputs):
+//   1-D (C = 1, experiments/models_gnn.py:1455-1456, 1514-1521):   out = (1 - scale) u[:, -1:] + cumsum(dt) (scale diff)
+//   2-D (C = 2, models_gnn2D.py:1291-1298, 1355-1366; rows of hd = double_mlp(h), component stride 164):
+//                                                                  out = (1 - scale) u + (cumsum(dt) scale) diff,  every column of u
+// with scale = gate(row[:82]), diff = diff(row[82:]); no sigmoid on scale, as in the reference.
+// Split like decoder_split_kernel: eight lanes per node, lane q builds the intermediate positions [q PP, (q + 1) PP) of all eight channels,
+// the node's 8 x L1 intermediates meet in the node's LDS table, lane q then forms OPL consecutive outputs of every component.  The two
+// networks run one after the other through the SAME table (a barrier after the reads of `gate` frees it for `diff`) and the lane keeps
+// the C x OPL outputs of `gate` in registers meanwhile: LDS, and with it the workgroups per CU, stay those of the one-network decoders, and
+// a network's 14-value windows (28 in 2-D) are dead before the other's are loaded.  The outputs are formed two intermediate channels at a
+// time: with all eight unrolled at once the compiler took 184 / 230 vector registers (1-D / 2-D), in pairs 73 / 115.
+// Rows are read with a caller-given stride `ld` as single floats: the second half of a row starts 328 bytes in, 8-byte aligned only.
+// Summation order (plain fp32 fmaf, no fp16 split: the range status word is not touched): an intermediate starts from its bias and adds the
+// taps of input component 0, then of component 1, ascending; an output adds, per intermediate channel, its taps ascending from 0, then the
+// eight channel sums as a tree (pairs, pairs of pairs, halves), then the bias; cumsum(dt) is formed by repeated float32 addition.
+// ----------------------------------------------------------------------------------------------
+struct DecNet {
+    const float* w1;     // [8][C][6]
+    const float* b1;     // [8]
+    const float* w2;     // [C][8][15]
+    const float* b2;     // [C]
+};
+
+struct DecGatedArgs {
+    const float* h;      // 1-D: [N, ld] rows of 164;  2-D: [N, ld] rows of 2 x 164 (hd)
+    long ld;             // row stride in floats
+    const float* u;      // [N, C tw]
+    long n_nodes;
+    DecNet gate, diff;
+    float dt;
+    float* out;          // [N, C tw]
+};
+
+// One network of lane q: o[co][i] = output t0 + i of component co.  row: the node's (clamped) row, already offset to the network's half;
+// component ci starts ci * CS floats further.  Ends with a barrier: the table may be written again.
+template <class G, int C, int CS, int R, int K1, int S1, int K2>
+__device__ __forceinline__ void decoder_gated_net(const float* row, float* mrow, int q, const DecNet& w, float (&o)[C][G::OPL]) {
+    constexpr int L1 = G::L1, PP = G::PP, XW = G::XW, OPL = G::OPL, MW4 = G::MW4, LP = G::LP;
+    const int p0 = q * PP;
+    float x[C][XW];
+#pragma unroll
+    for (int ci = 0; ci < C; ++ci) {
+        const int x0 = p0 * S1;
+#pragma unroll
+        for (int i = 0; i < XW; ++i) x[ci][i] = row[ci * CS + (x0 + i < R ? x0 + i : R - 1)];
+    }
+#pragma unroll 1
+    for (int c = 0; c < 8; ++c) {
+        const float bc = w.b1[c];
+        float s[PP];
+#pragma unroll
+        for (int pp = 0; pp < PP; ++pp) s[pp] = bc;
+#pragma unroll
+        for (int ci = 0; ci < C; ++ci) {
+            float wt[K1];
+#pragma unroll
+            for (int j = 0; j < K1; ++j) wt[j] = w.w1[(c * C + ci) * K1 + j];
+#pragma unroll
+            for (int j = 0; j < K1; ++j)
+#pragma unroll
+                for (int pp = 0; pp < PP; ++pp) s[pp] = fmaf(wt[j], x[ci][pp * S1 + j], s[pp]);
+        }
+#pragma unroll
+        for (int pp = 0; pp < PP; ++pp)
+            if (p0 + pp < L1) mrow[c * LP + p0 + pp] = swishf(s[pp]);
+    }
+    __syncthreads();        // every lane of a node's table has written before any reads
+    const int t0 = q * OPL;
+    float half[C][OPL], tot[C][OPL];
+#pragma unroll 1
+    for (int cp = 0; cp < 4; ++cp) {          // channel pairs one after the other: two channels' windows live at a time
+        float sc[C][2][OPL];                  // per component and channel of the pair: the tap sums of this lane's outputs
+#pragma unroll
+        for (int cc = 0; cc < 2; ++cc) {
+            const int c = 2 * cp + cc;
+            float m[4 * MW4];
+#pragma unroll
+            for (int i = 0; i < MW4; ++i) {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(mrow + c * LP + t0 + 4 * i);
+                m[4 * i] = v[0]; m[4 * i + 1] = v[1]; m[4 * i + 2] = v[2]; m[4 * i + 3] = v[3];
+            }
+#pragma unroll
+            for (int co = 0; co < C; ++co) {
+                float wt[K2];
+#pragma unroll
+                for (int j = 0; j < K2; ++j) wt[j] = w.w2[(co * 8 + c) * K2 + j];
+#pragma unroll
+                for (int i = 0; i < OPL; ++i) sc[co][cc][i] = 0.f;
+#pragma unroll
+                for (int j = 0; j < K2; ++j)
+#pragma unroll
+                    for (int i = 0; i < OPL; ++i) sc[co][cc][i] = fmaf(wt[j], m[i + j], sc[co][cc][i]);
+            }
+        }
+        // the eight channel sums as a tree: pairs, pairs of pairs, halves
+#pragma unroll
+        for (int co = 0; co < C; ++co)
+#pragma unroll
+            for (int i = 0; i < OPL; ++i) {
+                const float pair = sc[co][0][i] + sc[co][1][i];
+                if (cp & 1) {
+                    const float quad = half[co][i] + pair;
+                    tot[co][i] = cp == 1 ? quad : tot[co][i] + quad;
+                } else {
+                    half[co][i] = pair;
+                }
+            }
+    }
+#pragma unroll
+    for (int co = 0; co < C; ++co) {
+        const float b2v = w.b2[co];
+#pragma unroll
+        for (int i = 0; i < OPL; ++i) o[co][i] = tot[co][i] + b2v;
+    }
+    __syncthreads();        // every lane has read the table before the next network writes it
+}
+
+// C = 1: decoder_gated_kernel (rows of h), C = 2: decoder2d_gated_kernel (rows of hd)
+template <int C, int W, int TW, int K1, int S1, int K2>
+__device__ __forceinline__ void decoder_gated_body(const DecGatedArgs& a, float* mid) {
+    constexpr int R = W / 2;
+    using G = DecSplit<TW, K1, S1, K2, R>;
+    constexpr int OPL = G::OPL, LP = G::LP, NODES = G::NODES;
+    const int q = threadIdx.x & 7, nl = threadIdx.x >> 3;
+    const long n = (long)blockIdx.x * NODES + nl;
+    const long nc = n < a.n_nodes ? n : a.n_nodes - 1;          // lanes past the end: a valid row, nothing stored
+    const float* row = a.h + (size_t)nc * (size_t)a.ld;
+    float* mrow = mid + (size_t)nl * 8 * LP;
+    float scale[C][OPL], diff[C][OPL];
+#pragma unroll 1
+    for (int net = 0; net < 2; ++net) {                         // gate, then diff, through the same table
+        const DecNet w{net ? a.diff.w1 : a.gate.w1, net ? a.diff.b1 : a.gate.b1, net ? a.diff.w2 : a.gate.w2, net ? a.diff.b2 : a.gate.b2};
+        decoder_gated_net<G, C, W, R, K1, S1, K2>(row + net * R, mrow, q, w, diff);
+        if (net == 0) {
+#pragma unroll
+            for (int co = 0; co < C; ++co)
+#pragma unroll
+                for (int i = 0; i < OPL; ++i) scale[co][i] = diff[co][i];
+        }
+    }
+    const int t0 = q * OPL;
+    if (n >= a.n_nodes || t0 >= TW) return;
+    float tcum = 0.f;
+    for (int t = 0; t < t0; ++t) tcum += a.dt;          // cumsum of a constant, float32 partial sums like torch.cumsum on the device
+    const float* up = a.u + (size_t)n * C * TW;
+    float* op = a.out + (size_t)n * C * TW;
+    const float ul = C == 1 ? up[TW - 1] : 0.f;
+#pragma unroll
+    for (int i = 0; i < OPL; ++i) {
+        tcum += a.dt;
+        if (t0 + i < TW) {
+            if (C == 1) {
+                op[t0 + i] = (1.0f - scale[0][i]) * ul + tcum * (scale[0][i] * diff[0][i]);
+            } else {
+#pragma unroll
+                for (int co = 0; co < C; ++co) {
+                    const int k = co * TW + t0 + i;
+                    op[k] = (1.0f - scale[co][i]) * up[k] + (tcum * scale[co][i]) * diff[co][i];
+                }
+            }
+        }
+    }
+}
+
+template <int W, int TW, int K1, int S1, int K2>
+__global__ __launch_bounds__(256) void decoder_gated_kernel(DecGatedArgs a) {
+    using G = DecSplit<TW, K1, S1, K2, W / 2>;
+    __shared__ __attribute__((aligned(16))) float mid[G::NODES * 8 * G::LP];
+    decoder_gated_body<1, W, TW, K1, S1, K2>(a, mid);
+}
+
+template <int W, int TW, int K1, int S1, int K2>
+__global__ __launch_bounds__(256) void decoder2d_gated_kernel(DecGatedArgs a) {
+    using G = DecSplit<TW, K1, S1, K2, W / 2>;
+    __shared__ __attribute__((aligned(16))) float mid[G::NODES * 8 * G::LP];
+    decoder_gated_body<2, W, TW, K1, S1, K2>(a, mid);
+}
+
 }  // namespace msmp
 
 using namespace msmp;
@@ -272,3 +452,38 @@ extern "C" int msmp_decoder_f32(const float* h, const float* u, int64_t n_nodes,
     return check_launch("decoder_split_kernel");
 }
 #undef MSMP_DEC_SPLIT
+
+// The gated decoders exist for the one geometry the reference defines (hidden width 164, time_window 25): anything else is refused by
+// value before a launch, and the host keeps its PyTorch ops.  msmp_tune("wide_dec", ...) is read by the host only.
+static int decoder_gated(const char* who, bool two_d, const float* h, int ld, const float* u, int64_t n_nodes, int width, int tw,
+                         const DecNet& gate, const DecNet& diff, float dt, float* out, msmp_stream_t stream) {
+    MSMP_REQUIRE(h && u && out && gate.w1 && gate.b1 && gate.w2 && gate.b2 && diff.w1 && diff.b1 && diff.w2 && diff.b2, MSMP_ERR_ARG,
+                 "%s: null pointer", who);
+    MSMP_REQUIRE(n_nodes > 0 && n_nodes < (1L << 31), MSMP_ERR_ARG, "%s: bad n_nodes", who);
+    MSMP_REQUIRE(width == 164 && tw == 25, MSMP_ERR_UNSUPPORTED, "%s: width %d, time_window %d (the reference defines 164, 25)", who, width, tw);
+    const int comps = two_d ? 2 : 1;
+    MSMP_REQUIRE(ld >= comps * width, MSMP_ERR_ARG, "%s: row stride ld = %d < %d", who, ld, comps * width);
+    DecGatedArgs a{h, (long)ld, u, (long)n_nodes, gate, diff, dt, out};
+    using G = DecSplit<25, 6, 2, 15, 82>;
+    const dim3 grid((unsigned)((n_nodes + G::NODES - 1) / G::NODES)), block(G::NODES * 8);
+    hipStream_t st = (hipStream_t)stream;
+    timing_begin(MSMP_K_DECODER, st);
+    if (two_d) hipLaunchKernelGGL((decoder2d_gated_kernel<164, 25, 6, 2, 15>), grid, block, 0, st, a);      // models_gnn2D.py:1291-1298
+    else hipLaunchKernelGGL((decoder_gated_kernel<164, 25, 6, 2, 15>), grid, block, 0, st, a);              // models_gnn.py:1455-1456
+    timing_end(MSMP_K_DECODER, st);
+    return check_launch(two_d ? "decoder2d_gated_kernel" : "decoder_gated_kernel");
+}
+
+extern "C" int msmp_decoder_gated_f32(const float* h, int ld, const float* u, int64_t n_nodes, int width, int tw, const float* gate_w1,
+                                      const float* gate_b1, const float* gate_w2, const float* gate_b2, const float* diff_w1, const float* diff_b1,
+                                      const float* diff_w2, const float* diff_b2, float dt, float* out, msmp_stream_t stream) {
+    return decoder_gated("msmp_decoder_gated_f32", false, h, ld, u, n_nodes, width, tw, DecNet{gate_w1, gate_b1, gate_w2, gate_b2},
+                         DecNet{diff_w1, diff_b1, diff_w2, diff_b2}, dt, out, stream);
+}
+
+extern "C" int msmp_decoder2d_gated_f32(const float* hd, int ld, const float* u, int64_t n_nodes, int width, int tw, const float* gate_w1,
+                                        const float* gate_b1, const float* gate_w2, const float* gate_b2, const float* diff_w1, const float* diff_b1,
+                                        const float* diff_w2, const float* diff_b2, float dt, float* out, msmp_stream_t stream) {
+    return decoder_gated("msmp_decoder2d_gated_f32", true, hd, ld, u, n_nodes, width, tw, DecNet{gate_w1, gate_b1, gate_w2, gate_b2},
+                         DecNet{diff_w1, diff_b1, diff_w2, diff_b2}, dt, out, stream);
+}

@@ -28,6 +28,7 @@ from .graph import structure_of
 from .layers import GNN_Layer, GNN_LayerLin, Swish, mp_layer
 from .lem import LEM, LEMS
 from .reductions import bias_add
+from . import wide
 from .wide import _wide_fused, lemoutput_mlp
 
 _DECODER = {20: (15, 4, 10), 25: (16, 3, 14), 50: (12, 2, 10)}   # models_gnn.py:210-224; models_gnn2D.py:79-88
@@ -675,8 +676,10 @@ class _GLUBase(_SolverBase):
     gated pair of CNNs on the two halves of the hidden state,  out = (1 - scale) u_last + cumsum(dt) scale diff  with
     scale = output_mlp_gate(h[..., :82]), diff = output_mlp_diff(h[..., 82:])  (experiments/models_gnn.py:1379-1523,
     models_gnn2D.py:1198-1366; no sigmoid on `scale`, as in the reference).  Layers: the width-generic HIP path
-    (wide._mp_layer_wide); without grad the LEM recurrence is one HIP launch (msmp_lem_encoder_wide_f32) and lemoutput_mlp two HIP row
-    GEMMs; double_mlp and the two small CNNs: PyTorch-ROCm ops."""
+    (wide._mp_layer_wide); without grad the LEM recurrence is one HIP launch (msmp_lem_encoder_wide_f32), lemoutput_mlp two HIP row
+    GEMMs, double_mlp one (msmp_linear_f32) and the two small CNNs with the gated update one launch (msmp_decoder_gated_f32 /
+    msmp_decoder2d_gated_f32; switch "wide_dec").  Under autograd, with that switch or the fused width-generic path off, and at a width or
+    time window the entry refuses, the decoder is PyTorch-ROCm ops."""
     GATED, LEM_ENCODER, LAYER = True, True, GNN_LayerLin
 
     def __init__(self, pde, time_window=25, hidden_features=164, hidden_layer=6, eq_variables={}, save_state=None):
@@ -689,7 +692,28 @@ class _GLUBase(_SolverBase):
         self.output_mlp_gate = mk()
         self.output_mlp_diff = mk()
 
+    def _decode_hip(self, h, u, tw):
+        """The decoder as one HIP launch (2-D: behind double_mlp as one row GEMM), or None where the PyTorch ops below apply: under
+        autograd, for tensors the kernels do not read, with the switch "wide_dec" (or any switch of the fused width-generic path) off,
+        and at sizes the entry refuses by value."""
+        mods = (self.output_mlp_gate, self.output_mlp_diff) + ((self.double_mlp,) if self.TWO_D else ())
+        grad_path = torch.is_grad_enabled() and (h.requires_grad or any(p.requires_grad for m in mods for p in m.parameters()))
+        if grad_path or not (h.is_cuda and h.dtype == torch.float32 and u.is_cuda and u.dtype == torch.float32):
+            return None
+        W = h.shape[1]
+        if not _wide_fused(b'wide_dec') or getattr(self, '_dec_refused', None) == (W, tw):
+            return None
+        h, u = h.contiguous(), u.contiguous()
+        rows, ld = wide.double_mlp(self.double_mlp[0], h) if self.TWO_D else (h, W)
+        out = None if rows is None else wide.gated_decoder(rows, ld, u, W, tw, self.output_mlp_gate, self.output_mlp_diff, self.pde.dt, self.TWO_D)
+        if out is None:
+            self._dec_refused = (W, tw)         # refused by value: these sizes are not asked again (in 2-D each try costs a row GEMM)
+        return out
+
     def _decode(self, h, u, u_in, dt, tw):
+        out = self._decode_hip(h, u, tw)
+        if out is not None:
+            return out.to(u_in.dtype)
         half = h.shape[1] // 2
         if self.TWO_D:                  # models_gnn2D.py:1349-1366
             hd = self.double_mlp(h)                                             # [N, 2, W]
