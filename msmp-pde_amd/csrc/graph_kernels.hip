@@ -239,12 +239,12 @@ extern "C" int msmp_knn_graph_f64(const double* x, int dim, const int32_t* graph
     MSMP_REQUIRE(dim >= 1 && dim <= MAX_DIM && n_graphs > 0 && n_nodes > 0 && n_nodes < (1L << 31) && n_edges >= 0,
                  MSMP_ERR_ARG, "msmp_knn_graph_f64: bad sizes");
     MSMP_REQUIRE(k >= 1 && k <= MAX_K, MSMP_ERR_UNSUPPORTED, "msmp_knn_graph_f64: k=%d outside 1..%d", k, MAX_K);
+    MSMP_REQUIRE(n_edges == 0 || edge_index_out, MSMP_ERR_ARG, "msmp_knn_graph_f64: null output");   // refused before anything is launched
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = (unsigned)((n_nodes + 255) / 256);
     hipLaunchKernelGGL(knn_degree_kernel, dim3(grid), dim3(256), 0, st, graph_ptr, (int)n_graphs, (int)n_nodes, k, rowptr_out);
     hipLaunchKernelGGL(exclusive_scan_inplace_kernel, dim3(1), dim3(1024), 0, st, rowptr_out, (int)n_nodes);
     if (n_edges == 0) return check_launch("knn_degree_kernel");
-    MSMP_REQUIRE(edge_index_out, MSMP_ERR_ARG, "msmp_knn_graph_f64: null output");
     hipLaunchKernelGGL(knn_kernel, dim3(grid), dim3(256), 0, st, x, dim, graph_ptr, (int)n_graphs, (int)n_nodes, k,
                        (long)n_edges, (const int*)rowptr_out, edge_index_out);
     return check_launch("knn_kernel");

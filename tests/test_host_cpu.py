@@ -147,6 +147,33 @@ def test_graph_creator_mirror_tensors(mp, exp):
         assert np.array_equal(getattr(g2, k).numpy(), getattr(ref2, k)), k
 
 
+@pytest.mark.parametrize('shape', [(5, 40, 7), (3, 40, 2, 7)], ids=['scalar', 'two-component'])
+def test_create_data_window_slice_and_gather_equal_the_oracle(mp, shape):
+    """GraphCreator.create_data: with every sample at the same step the window is a zero-copy slice of the trajectories, with the steps
+    as a tensor (or mixed) it is one gather; both are the oracle's windows -- at s0 = tw and s0 = nt - tw (the two inclusive bounds of the
+    slice condition) and in between."""
+    from oracle import msmp_oracle as O
+    from msmp_pde_amd.synthetic import make_pde
+    tw, (bsz, nt) = 6, shape[:2]
+    u = torch.tensor(np.random.default_rng(2).standard_normal(shape))
+    gc = mp.GraphCreator(make_pde('E2' if len(shape) == 3 else 'MSWG3', nt, shape[-1]), neighbors=3, time_window=tw, device='cpu')
+    for s0 in (tw, 17, nt - tw):
+        steps = [s0] * bsz
+        want = O.create_data(u.numpy(), steps, tw)
+        sliced = gc.create_data(u, steps)
+        gathered = gc.create_data(u, torch.tensor(steps))
+        for got_s, got_g, ref in zip(sliced, gathered, want):
+            assert got_s._base is u and got_s.data_ptr() >= u.data_ptr()            # a view of the trajectories: nothing was copied
+            assert got_g._base is not u                                             # the gather made a tensor of its own
+            assert np.array_equal(got_s.numpy(), ref) and np.array_equal(got_g.numpy(), ref), s0
+    steps = [tw, nt - tw, 17, 9, 30][:bsz]
+    assert len(set(steps)) > 1
+    for got, ref in zip(gc.create_data(u, steps), O.create_data(u.numpy(), steps, tw)):
+        assert got._base is not u and np.array_equal(got.numpy(), ref)
+    for got, ref in zip(gc.create_data(u, torch.tensor(steps)), O.create_data(u.numpy(), steps, tw)):
+        assert np.array_equal(got.numpy(), ref)
+
+
 @pytest.mark.parametrize('kind', ['MP_PDE_Solver', 'MP_PDE_SolverGated', 'MP_PDE_Solver2D', 'MP_PDE_Solver2DGated'])
 def test_state_dict_is_reference_compatible(mp, kind):
     """Checkpoint compatibility: the drop-in class has exactly the reference's state_dict keys and shapes."""
