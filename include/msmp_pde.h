@@ -94,6 +94,9 @@ int msmp_last_status(int* flags_out, int reset);
  *             workgroups only (same bits either way).
  *   "lem_wide" 1 (default): the host's no-grad LEM at widths other than 128 is one msmp_lem_encoder_wide_f32 launch; 0: the loop of two
  *             library GEMMs + msmp_wide_lem_z_f32 / _y_f32 per time step (the entry itself does not read the key).
+ *   "lem_wide_train" 1 (default): under autograd the host's LEM at widths other than 128 is msmp_lem_train_fwd_wide_f32 + msmp_lem_train_bwd_wide_f32 +
+ *             one msmp_grad_weights_cat_f32; 0: the PyTorch ops of the restated cell, differentiated by autograd (the entries themselves do
+ *             not read the key; any value other than 0 selects the kernels).
  *   "wide_msg" 1 (default): the host's no-grad layer at widths other than 128 evaluates the message half of a head as one
  *             msmp_wide_message_f32 launch; 0: msmp_wide_gather_swish_f32 + msmp_linear_f32 + msmp_wide_scatter_mean_f32 around two
  *             [E, ld] tensors (the entry itself does not read the key).  The host takes the fused launch only while "split" and
@@ -553,6 +556,33 @@ int msmp_pack_lem_wide_f32(const float* weights, const float* weights_lin_z, con
  * required pointer; n_nodes = 0 is a no-op.  A step input with |x| > 255 or not finite raises MSMP_STATUS_INPUT_RANGE. */
 int msmp_lem_encoder_wide_f32(const float* xin, int64_t n_nodes, int t_len, int ninp, int width, float dt, const float* packed,
                               const float* y0, const float* z0, float* y_out, float* z_out, msmp_stream_t stream);
+/* The TRAINING pair of that cell at any hidden width 1 <= width <= 256 (lem_wide_train_kernel.hip): msmp_lem_train_fwd_f32 / _bwd_f32 with the
+ * width as an argument, Wp = 32 ceil(width / 32), ldg = 128 ceil(width / 128).  Three-way bf16 split products (fp32-exact, as the 128-wide
+ * pair): no input range, the range status is neither read nor raised.  Blobs: weights [3 width, width + ninp], weights_lin_z
+ * [width, width + ninp], bias [3 width], bias_lin_z [width], ninp 1..8;
+ *   msmp_packed_lem_wide_train_floats = 6144 kt^2 + 1152 kt, msmp_packed_lem_wide_bwd_floats = 6144 kt^2 floats (kt = ceil(width / 32)),
+ * 0 (and msmp_last_error) for a width or ninp outside the range.  All blobs, `saved` and `dg_out` are 16-byte aligned. */
+int64_t msmp_packed_lem_wide_train_floats(int ninp, int width);
+int msmp_pack_lem_wide_train_f32(const float* weights, const float* weights_lin_z, const float* bias, const float* bias_lin_z, int ninp,
+                                 int width, float* packed_out, msmp_stream_t stream);
+int64_t msmp_packed_lem_wide_bwd_floats(int ninp, int width);
+int msmp_pack_lem_wide_bwd_f32(const float* weights, const float* weights_lin_z, int ninp, int width, float* packed_out, msmp_stream_t stream);
+/* saved [6][n_nodes][t_len][Wp] floats: dt*sigmoid(g2), tanh(g3), dt*sigmoid(g1), tanh(lin), y_{t-1}, z_t (every element is written);
+ * dg [n_nodes][t_len][4][ldg] floats.  0 (and msmp_last_error) for a width outside 1..256, n_nodes < 0 or t_len < 1. */
+int64_t msmp_lem_wide_saved_floats(int64_t n_nodes, int t_len, int width);
+int64_t msmp_lem_wide_dg_floats(int64_t n_nodes, int t_len, int width);
+/* xin [n_nodes, t_len, msmp_lem_input_stride(ninp)]; y0 / z0 [n_nodes, width] (both NULL = zeros) -> y_out, z_out (or NULL) dense
+ * [n_nodes, width]; saved may be NULL when no backward follows (the state-carrying LEMS under no_grad).  MSMP_ERR_UNSUPPORTED for width
+ * outside 1..256 or ninp outside 1..8; MSMP_ERR_ARG for t_len < 1, a null required pointer, one initial state without the other or a
+ * misaligned blob / saved; n_nodes = 0 is a no-op. */
+int msmp_lem_train_fwd_wide_f32(const float* xin, int64_t n_nodes, int t_len, int ninp, int width, float dt, const float* packed,
+                                const float* y0, const float* z0, float* saved, float* y_out, float* z_out, msmp_stream_t stream);
+/* grad_y [n_nodes, width] = dL/dy_T -> dg_out: per node and step the gates (g1 | g2 | g3 | lin), ldg columns each, columns width .. ldg - 1
+ * written as 0, so every gate is one or two 128-column A operands (row stride 4 ldg) of msmp_grad_weights_cat_f32 with B = [plane 4 (lin:
+ * plane 5) of saved, row stride Wp | x_t].  y0 / z0: the forward's initial states (both or none).  Also MSMP_ERR_ARG for dt = 0.  No
+ * gradient of the step inputs or of the initial states, as at 128. */
+int msmp_lem_train_bwd_wide_f32(const float* grad_y, const float* saved, const float* y0, const float* z0, int64_t n_nodes, int t_len,
+                                int width, float dt, const float* packed_bwd, float* dg_out, msmp_stream_t stream);
 /* The message half of one head at any hidden width 1 <= width <= 256 in ONE launch, nothing edge-sized in memory
  * (experiments/models_gnn.py:132-138 message with message_net_1 factorised per node into p / q, :107 aggr = 'mean'):
  *   agg_out[n][c] = (1 / max(deg n, 1)) sum_{r in CSR row n} Swish(b2[c] + sum_k w2[c][k] Swish(p[n][k] + q[col[r]][k])),   c < width,

@@ -105,6 +105,14 @@ SIGNATURES = {
     'msmp_packed_lem_wide_floats': (c_int64, [c_int, c_int]),
     'msmp_pack_lem_wide_f32': (c_int, [c_void_p] * 4 + [c_int, c_int, c_void_p, c_void_p]),
     'msmp_lem_encoder_wide_f32': (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_float] + [c_void_p] * 6),
+    'msmp_packed_lem_wide_train_floats': (c_int64, [c_int, c_int]),
+    'msmp_pack_lem_wide_train_f32': (c_int, [c_void_p] * 4 + [c_int, c_int, c_void_p, c_void_p]),
+    'msmp_packed_lem_wide_bwd_floats': (c_int64, [c_int, c_int]),
+    'msmp_pack_lem_wide_bwd_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    'msmp_lem_wide_saved_floats': (c_int64, [c_int64, c_int, c_int]),
+    'msmp_lem_wide_dg_floats': (c_int64, [c_int64, c_int, c_int]),
+    'msmp_lem_train_fwd_wide_f32': (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_float] + [c_void_p] * 7),
+    'msmp_lem_train_bwd_wide_f32': (c_int, [c_void_p] * 4 + [c_int64, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     'msmp_packed_wide_msg_floats': (c_int64, [c_int]),
     'msmp_pack_wide_msg_f32': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'msmp_wide_message_max_in_degree': (c_int, [c_int]),

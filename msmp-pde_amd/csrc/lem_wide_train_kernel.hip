@@ -1,0 +1,520 @@
+// LEM encoder for TRAINING at ANY hidden width 1 <= W <= 256 (the GLU classes: 164): the width-generic counterparts of lem_train_fwd_kernel
+// and lem_bptt_kernel (lem_train_kernel.hip; its header comment states the cell, the backward recurrences and the saved set).
+//   msmp_lem_train_fwd_wide_f32   the T-step recurrence from (y0, z0) to (y_T, z_T), saving per step a2, c, a1, d, y_{t-1}, z'
+//   msmp_lem_train_bwd_wide_f32   back-propagation through time: dL/dy_T -> dG = (dg1 | dg2 | dg3 | dl) per node and step
+// The weight gradients are then msmp_grad_weights_cat_f32 jobs over the N*T rows (128 columns of dG each), issued by the host layer.
+//
+// Workgroup shape (the 128-wide one with the 4 waves replaced by KT = ceil(W / 32)): one 32-node tile per workgroup, 64 KT threads; wave ct owns
+// channel tile ct (32 of the Wp = 32 KT channels) of every carried tensor, in accumulator layout, for all T steps.  The B operand of a GEMM
+// (y, z' forward; dg1, dl, dg2, dg3 backward) is PUBLISHED in LDS as bf16 hi / mid / lo fragments in acc order (6 KB per k-tile, 6 KT KB per
+// tensor; ONE area, reused between barriers as in lem_bptt_kernel), and every wave multiplies its own 32 rows of the weight block -- bf16x3
+// A fragments streamed from the L2-resident blob through buffer loads, one k-tile (6 KB per wave) ahead -- with all published fragments: six
+// v_mfma_f32_32x32x16_bf16 per K = 16 step, fp32-exact products (mfma_tiles.h).  No fp16 anywhere, so there is no input range and the
+// kernels neither read nor raise the range status.  Barriers per step: 4 forward, 8 backward.
+// Channels W .. Wp - 1 carry zero weights, zero bias and zero state: their z and y stay exact zeros, their dG is an exact zero, and they are
+// never written to y_out / z_out.  A node's arithmetic depends on nothing but its own row.
+//
+// Memory layouts (all fp32):
+//   saved  [6][N][T][Wp]            planes a2, c, a1, d, y_{t-1}, z'; every element is written (pad channels: dt / 2 in a1, a2; 0 elsewhere)
+//   dG     [N][T][4][ldg]           ldg = 128 ceil(W / 128); gate order g1, g2, g3, lin; columns W .. ldg - 1 are written as 0
+#include "lem_layout.h"
+#include "wide_frags.h"
+
+namespace msmp {
+
+enum { LWT_A2 = 0, LWT_C = 1, LWT_A1 = 2, LWT_D = 3, LWT_Y = 4, LWT_Z = 5, LWT_PLANES = 6 };
+constexpr int LWT_KTILE_U4 = 2 * 3 * 64;                  // one k-tile of a fragment stream or of a published tensor: [s 2][plane 3][lane 64] u32x4, 6 KB
+constexpr int LWT_KTILE_FLOATS = LWT_KTILE_U4 * 4;
+
+// forward blob (floats), kt = ceil(W / 32), Wp = 32 kt:
+//   rec  [wave ct kt][gate 4: g2, g3, g1, lin][k-tile kc kt][s 2][plane 3: hi, mid, lo][lane 64][8 bf16]: rows 32 ct .. of the gate's recurrent
+//        block, columns 32 kc .., as bf16x3 A fragments in acc order (split_k_acc); a wave's stream of one time step is contiguous |
+//   wx   [gate 4][ct kt][s 4][lane 64]: the input columns as v_mfma_f32_32x32x2_f32 A fragments, W_gate[32 ct + (lane & 31)][W + 2 s + (lane >> 5)] |
+//   bias [gate 4][Wp]
+// zero outside the matrices.
+struct LemWideTrainLayout {
+    int64_t rec, wx, bias, total;
+};
+__host__ __device__ inline LemWideTrainLayout lem_wide_train_layout(int kt) {
+    LemWideTrainLayout L;
+    L.rec = 0;
+    L.wx = L.rec + (int64_t)4 * kt * kt * LWT_KTILE_FLOATS;
+    L.bias = L.wx + (int64_t)4 * kt * 256;
+    L.total = L.bias + (int64_t)4 * kt * 32;
+    return L;
+}
+// backward blob (floats): rec_t [wave ct kt][gate 4: g1, lin, g2, g3 (consumption order)][k-tile kc kt][s 2][plane 3][lane 64][8 bf16]:
+//   fragment row 32 ct + m, column 32 kc + kk  =  M_gate[32 kc + kk][32 ct + m], M the gate's recurrent block: the TRANSPOSED blocks
+__host__ __device__ inline int64_t lem_wide_bwd_floats(int kt) { return (int64_t)4 * kt * kt * LWT_KTILE_FLOATS; }
+
+struct LemWideTrainPackArgs {
+    const float *w, *wz, *b, *bz;
+    int ninp, width, kt;
+    float* out;
+};
+
+// recurrent / input weight of `row` (< W) of forward gate g (0 g2, 1 g3, 2 g1, 3 lin), column col.  ONE load from a selected matrix and
+// first row: as a chain of four conditional loads the wx loop below was compiled into divergent blocks in which the lanes of gate 3 reached
+// the load with neither the matrix nor the row assigned (read in the gfx950 assembly: a wild address, the kernel faulted on first use).
+__device__ __forceinline__ float lwt_weight(const LemWideTrainPackArgs& a, int g, int row, int col) {
+    const int kin = a.width + a.ninp;
+    const float* m = g == 3 ? a.wz : a.w;
+    const int first = g == 0 ? a.width : g == 1 ? 2 * a.width : 0;
+    return m[(size_t)(first + row) * kin + col];
+}
+__device__ __forceinline__ float lwt_bias(const LemWideTrainPackArgs& a, int g, int row) {
+    const float* m = g == 3 ? a.bz : a.b;
+    const int first = g == 0 ? a.width : g == 1 ? 2 * a.width : 0;
+    return m[first + row];
+}
+
+__device__ __forceinline__ void lwt_store_b3(float* base, int64_t frag /* (stream, s) */, int lane, const float (&v)[8]) {
+    const Bf3 f = split_bf16x3(v);
+    u32x4* dst = reinterpret_cast<u32x4*>(base) + frag * 3 * 64 + lane;
+    dst[0] = __builtin_bit_cast(u32x4, f.hi);
+    dst[64] = __builtin_bit_cast(u32x4, f.mid);
+    dst[128] = __builtin_bit_cast(u32x4, f.lo);
+}
+
+// TRANSPOSED = false: the forward blob; true: the backward blob (a.b / a.bz unused).  One thread per (ct, gate, kc, s, lane).
+template <bool TRANSPOSED>
+__global__ __launch_bounds__(256) void pack_lem_wide_train_kernel(LemWideTrainPackArgs a) {
+    const int kt = a.kt, W = a.width;
+    const int64_t tid0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t n_rec = (int64_t)4 * kt * kt * 2 * 64;
+    for (int64_t p = tid0; p < n_rec; p += stride) {
+        const int lane = (int)(p & 63), s = (int)(p >> 6) & 1;
+        const int64_t q = p >> 7;
+        const int kc = (int)(q % kt), g = (int)((q / kt) & 3), ct = (int)(q / (4 * kt));
+        const int row = 32 * ct + (lane & 31);
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int k = 32 * kc + split_k_acc(s, lane >> 5, j);
+            if (row >= W || k >= W) v[j] = 0.f;
+            else if (!TRANSPOSED) v[j] = lwt_weight(a, g, row, k);
+            else v[j] = lwt_weight(a, g == 0 ? 2 : g == 1 ? 3 : g == 2 ? 0 : 1, k, row);      // g1, lin, g2, g3 in forward numbering
+        }
+        lwt_store_b3(a.out, p >> 6, lane, v);
+    }
+    if (TRANSPOSED) return;
+    const LemWideTrainLayout L = lem_wide_train_layout(kt);
+    for (int64_t p = tid0; p < (int64_t)4 * kt * 256; p += stride) {
+        const int lane = (int)(p & 63), s = (int)(p >> 6) & 3, ct = (int)((p >> 8) % kt), g = (int)((p >> 8) / kt);
+        const int row = 32 * ct + (lane & 31), f = 2 * s + (lane >> 5);
+        a.out[L.wx + p] = row < W && f < a.ninp ? lwt_weight(a, g, row, W + f) : 0.f;
+    }
+    for (int64_t p = tid0; p < (int64_t)4 * kt * 32; p += stride) {
+        const int row = (int)(p % (32 * kt)), g = (int)(p / (32 * kt));
+        a.out[L.bias + p] = row < W ? lwt_bias(a, g, row) : 0.f;
+    }
+}
+
+// ---- the pieces both kernels share ------------------------------------------------------------------------------------------------
+
+// one tile of a 16-byte aligned row <-> accumulator registers: register 4 q + m is channel 32 ct + 8 q + 4 hh + m (row_hh = row + 4 hh)
+__device__ __forceinline__ void lwt_tile_load(const float* row_hh, int ct, f32x16& v) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const f32x4 p = *reinterpret_cast<const f32x4*>(row_hh + 32 * ct + 8 * q);
+#pragma unroll
+        for (int m = 0; m < 4; ++m) v[4 * q + m] = p[m];
+    }
+}
+__device__ __forceinline__ void lwt_tile_store(float* row_hh, int ct, const f32x16& v) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        f32x4 p;
+#pragma unroll
+        for (int m = 0; m < 4; ++m) p[m] = v[4 * q + m];
+        *reinterpret_cast<f32x4*>(row_hh + 32 * ct + 8 * q) = p;
+    }
+}
+// the same against a DENSE row of W floats (states, dL/dy_T: any alignment); channels >= W read as 0 and are not written
+__device__ __forceinline__ void lwt_dense_load(const float* row, int ct, int hh, int W, f32x16& v) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int ch = 32 * ct + acc_row(r, hh);
+        v[r] = ch < W ? row[ch] : 0.f;
+    }
+}
+__device__ __forceinline__ void lwt_dense_store(float* row, int ct, int hh, int W, const f32x16& v) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int ch = 32 * ct + acc_row(r, hh);
+        if (ch < W) row[ch] = v[r];
+    }
+}
+
+__device__ __forceinline__ void lwt_publish(u32x4* xf, int ct, int lane, const f32x16& v) {
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        float t[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) t[j] = v[8 * s + j];
+        const Bf3 f = split_bf16x3(t);
+        u32x4* dst = xf + (size_t)((ct * 2 + s) * 3) * 64 + lane;
+        dst[0] = __builtin_bit_cast(u32x4, f.hi);
+        dst[64] = __builtin_bit_cast(u32x4, f.mid);
+        dst[128] = __builtin_bit_cast(u32x4, f.lo);
+    }
+}
+
+struct LwtFrag {
+    u32x4 f[2][3];       // [s][plane] of this wave's 32 rows of one k-tile
+};
+// k-tile i of this wave's stream (4 KT per time step) through BUFFER loads: the descriptor holds the wave's stream base (scalar), the
+// fragment is a scalar offset and the lane one 32-bit vector offset (with global loads the compiler forms, hoists and spills a 64-bit
+// address per fragment: lem_train_kernel.hip)
+__device__ __forceinline__ void lwt_frag_load(LwtFrag& w, __amdgpu_buffer_rsrc_t stream, int i, unsigned loff) {
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl) w.f[s][pl] = __builtin_amdgcn_raw_buffer_load_b128(stream, loff, ((i * 2 + s) * 3 + pl) * 1024, 0);
+}
+template <int KT>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t lwt_stream(const float* rec, int ct_uniform) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(rec + (size_t)ct_uniform * (4 * KT * LWT_KTILE_FLOATS)), 0, 4 * KT * LWT_KTILE_FLOATS * 4,
+                                             0x00027000);
+}
+// acc (tile ct) += W[32 ct .., k-tile kc] * published[k-tile kc]
+__device__ __forceinline__ void lwt_mma(const LwtFrag& w, const u32x4* xf, int kc, int lane, f32x16& acc) {
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const bf16x8 wh = __builtin_bit_cast(bf16x8, w.f[s][0]), wm = __builtin_bit_cast(bf16x8, w.f[s][1]), wl = __builtin_bit_cast(bf16x8, w.f[s][2]);
+        const u32x4* b = xf + (size_t)((kc * 2 + s) * 3) * 64 + lane;
+        const bf16x8 bh = __builtin_bit_cast(bf16x8, b[0]), bm = __builtin_bit_cast(bf16x8, b[64]), bl = __builtin_bit_cast(bf16x8, b[128]);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, bh, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, bl, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, bm, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, bh, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, bm, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, bh, acc, 0, 0, 0);
+    }
+}
+// one GEMM: the KT k-tiles of gate GRP (stream position) against the tensor currently published.  The k-tile after each one is requested
+// before its MFMAs (the first of the next gate after the last; after gate 3 the stream wraps to the next time step), so a GEMM starts with
+// its first k-tile in registers.  wA / wB alternate by stream index (4 KT is even: index 0 is always wA).
+template <int KT, int GRP>
+__device__ __forceinline__ void lwt_gemm(LwtFrag& wA, LwtFrag& wB, __amdgpu_buffer_rsrc_t stream, const u32x4* xf, int lane, unsigned loff, f32x16& acc) {
+#pragma unroll
+    for (int kc = 0; kc < KT; ++kc) {
+        const int i = GRP * KT + kc;
+        LwtFrag& cur = (i & 1) ? wB : wA;
+        LwtFrag& nxt = (i & 1) ? wA : wB;
+        lwt_frag_load(nxt, stream, (i + 1) % (4 * KT), loff);
+        lwt_mma(cur, xf, kc, lane, acc);
+        __builtin_amdgcn_sched_barrier(0);       // one k-tile of weight fragments ahead, not all of them
+    }
+}
+
+struct LemWideTrainArgs {
+    const float* xin;       // [N, T, stride]
+    long n_nodes;
+    int t_len, stride, width;
+    float dt;
+    const float *rec, *wx, *bias;
+    float* saved;           // [6][N][T][Wp] or NULL
+    const float *y0, *z0;   // [N, W] or NULL (zeros)
+    float *y_out, *z_out;   // [N, W]; z_out may be NULL
+};
+
+// acc (tile ct) = bias + W[:, W : W + ninp] x_t: the input columns as up to four fp32 MFMA k-steps (x[] is zero past ninp)
+template <int KT>
+__device__ __forceinline__ void lwt_tile_init(const LemWideTrainArgs& a, int g, int ct, int lane, int hh, int ns, const float (&x)[8], f32x16& acc) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const f32x4 bv = *reinterpret_cast<const f32x4*>(a.bias + (g * KT + ct) * 32 + 8 * q + 4 * hh);
+#pragma unroll
+        for (int m = 0; m < 4; ++m) acc[4 * q + m] = bv[m];
+    }
+    const float* wf = a.wx + (size_t)(g * KT + ct) * 256 + lane;
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+        if (s < ns) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[s * 64], hh ? x[2 * s + 1] : x[2 * s], acc, 0, 0, 0);
+}
+
+template <int KT>
+__global__ __launch_bounds__(64 * KT) void lem_wide_train_fwd_kernel(LemWideTrainArgs a) {
+    constexpr int WP = 32 * KT;
+    __shared__ u32x4 xf[KT * LWT_KTILE_U4];                          // 6 KT KB: y, then z', alternately
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int ct = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int c = lane & 31, hh = lane >> 5, W = a.width, ns = a.stride >> 1;
+    const size_t plane = (size_t)a.n_nodes * a.t_len * WP;
+    const __amdgpu_buffer_rsrc_t stream = lwt_stream<KT>(a.rec, ct);
+    const long n = (long)blockIdx.x * 32 + c;
+    const bool live = n < a.n_nodes;
+    const long nc = live ? n : a.n_nodes - 1;
+    const bool save = live && a.saved != nullptr;
+    const float* xrow = a.xin + (size_t)nc * a.t_len * a.stride;
+    float* srow = a.saved + (size_t)nc * a.t_len * WP + 4 * hh;
+
+    f32x16 y, z, g, acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { y[r] = 0.f; z[r] = 0.f; }
+    if (a.y0) lwt_dense_load(a.y0 + (size_t)nc * W, ct, hh, W, y);
+    if (a.z0) lwt_dense_load(a.z0 + (size_t)nc * W, ct, hh, W, z);
+    lwt_publish(xf, ct, lane, y);
+    LwtFrag wA, wB;
+    unsigned loff = 16u * lane;
+    asm volatile("" : "+v"(loff));
+    lwt_frag_load(wA, stream, 0, loff);
+    __syncthreads();
+
+    for (int t = 0; t < a.t_len; ++t) {
+        float x[8];
+#pragma unroll
+        for (int f = 0; f < 8; ++f) x[f] = f < a.stride ? xrow[(size_t)t * a.stride + f] : 0.f;
+        float* st = srow + (size_t)t * WP;
+
+        if (save) lwt_tile_store(st + LWT_Y * plane, ct, y);        // y_{t-1}, the state ENTERING the step
+        lwt_tile_init<KT>(a, 0, ct, lane, hh, ns, x, g);             // g2 -> a2            (published: y)
+        lwt_gemm<KT, 0>(wA, wB, stream, xf, lane, loff, g);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) g[r] = a.dt * sigmoidf_(g[r]);
+        if (save) lwt_tile_store(st + LWT_A2 * plane, ct, g);
+        lwt_tile_init<KT>(a, 1, ct, lane, hh, ns, x, acc);           // g3 -> c, z'
+        lwt_gemm<KT, 1>(wA, wB, stream, xf, lane, loff, acc);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            acc[r] = tanhf_(acc[r]);
+            z[r] = (1.0f - g[r]) * z[r] + g[r] * acc[r];
+        }
+        if (save) {
+            lwt_tile_store(st + LWT_C * plane, ct, acc);
+            lwt_tile_store(st + LWT_Z * plane, ct, z);
+        }
+        lwt_tile_init<KT>(a, 2, ct, lane, hh, ns, x, g);             // g1 -> a1
+        lwt_gemm<KT, 2>(wA, wB, stream, xf, lane, loff, g);
+        __syncthreads();                                             // every wave has read the last fragment of y
+#pragma unroll
+        for (int r = 0; r < 16; ++r) g[r] = a.dt * sigmoidf_(g[r]);
+        if (save) lwt_tile_store(st + LWT_A1 * plane, ct, g);
+        lwt_publish(xf, ct, lane, z);
+        lwt_tile_init<KT>(a, 3, ct, lane, hh, ns, x, acc);           // lin -> d, y'        (published: z')
+        __syncthreads();
+        lwt_gemm<KT, 3>(wA, wB, stream, xf, lane, loff, acc);
+        __syncthreads();                                             // every wave has read the last fragment of z'
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            acc[r] = tanhf_(acc[r]);
+            y[r] = (1.0f - g[r]) * y[r] + g[r] * acc[r];
+        }
+        if (save) lwt_tile_store(st + LWT_D * plane, ct, acc);
+        lwt_publish(xf, ct, lane, y);
+        __syncthreads();
+    }
+    if (live) {
+        lwt_dense_store(a.y_out + (size_t)n * W, ct, hh, W, y);
+        if (a.z_out) lwt_dense_store(a.z_out + (size_t)n * W, ct, hh, W, z);
+    }
+}
+
+struct LemWideBwdArgs {
+    const float* gout;      // [N, W] dL/dy_T
+    const float* saved;     // [6][N][T][Wp]
+    long n_nodes;
+    int t_len, width, ldg;
+    float dt;
+    const float* rec_t;
+    float* dg;              // [N][T][4][ldg]
+    const float* z0;        // the forward's initial z [N, W] (NULL = zeros); y0 is in the saved y plane
+};
+
+template <int KT>
+__global__ __launch_bounds__(64 * KT) void lem_wide_bptt_kernel(LemWideBwdArgs a) {
+    constexpr int WP = 32 * KT;
+    __shared__ u32x4 xf[KT * LWT_KTILE_U4];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int ct = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int c = lane & 31, hh = lane >> 5, W = a.width, ldg = a.ldg;
+    const size_t plane = (size_t)a.n_nodes * a.t_len * WP;
+    const __amdgpu_buffer_rsrc_t stream = lwt_stream<KT>(a.rec_t, ct);
+    const float inv_dt = 1.0f / a.dt;
+    const long n = (long)blockIdx.x * 32 + c;
+    const bool live = n < a.n_nodes;
+    const long nc = live ? n : a.n_nodes - 1;
+    const float* srow = a.saved + (size_t)nc * a.t_len * WP + 4 * hh;
+    float* grow = a.dg + (size_t)nc * a.t_len * (4 * ldg) + 4 * hh;
+    f32x16 dy, dz, p, q;
+    lwt_dense_load(a.gout + (size_t)nc * W, ct, hh, W, dy);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) dz[r] = 0.f;
+    LwtFrag wA, wB;
+    unsigned loff = 16u * lane;
+    asm volatile("" : "+v"(loff));
+    lwt_frag_load(wA, stream, 0, loff);
+
+    for (int t = a.t_len - 1; t >= 0; --t) {
+        const float* st = srow + (size_t)t * WP;
+        float* gt = grow + (size_t)t * (4 * ldg);
+        {   // y' = (1-a1) y + a1 d:  p = dg1, q = dl
+            f32x16 a1, d, yp;
+            lwt_tile_load(st + LWT_A1 * plane, ct, a1);
+            lwt_tile_load(st + LWT_D * plane, ct, d);
+            lwt_tile_load(st + LWT_Y * plane, ct, yp);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float gr = dy[r];
+                q[r] = gr * a1[r] * (1.0f - d[r] * d[r]);
+                p[r] = gr * (d[r] - yp[r]) * a1[r] * (1.0f - a1[r] * inv_dt);
+                dy[r] = gr * (1.0f - a1[r]);
+            }
+        }
+        if (live) {
+            lwt_tile_store(gt, ct, p);
+            lwt_tile_store(gt + 3 * ldg, ct, q);
+            // columns Wp .. ldg - 1 of all four gates: zeros (the weight-gradient jobs read whole 128-column blocks)
+            f32x16 zero;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) zero[r] = 0.f;
+            for (int T2 = KT + ct; T2 < (ldg >> 5); T2 += KT)
+#pragma unroll
+                for (int gi = 0; gi < 4; ++gi) lwt_tile_store(gt + gi * ldg, T2, zero);
+        }
+        lwt_publish(xf, ct, lane, p);            // the area is free: the previous GEMM ended with a barrier
+        __syncthreads();
+        lwt_gemm<KT, 0>(wA, wB, stream, xf, lane, loff, dy);         // dy += W_g1^T dg1
+        __syncthreads();
+        lwt_publish(xf, ct, lane, q);
+        __syncthreads();
+        lwt_gemm<KT, 1>(wA, wB, stream, xf, lane, loff, dz);         // dz += Wz^T dl
+        __syncthreads();
+        {   // z' = (1-a2) z + a2 c:  p = dg2, q = dg3
+            f32x16 a2, cc, zp;
+            lwt_tile_load(st + LWT_A2 * plane, ct, a2);
+            lwt_tile_load(st + LWT_C * plane, ct, cc);
+            if (t > 0) lwt_tile_load(st - WP + LWT_Z * plane, ct, zp);
+            else if (a.z0) lwt_dense_load(a.z0 + (size_t)nc * W, ct, hh, W, zp);
+            else {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) zp[r] = 0.f;
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float gr = dz[r];
+                q[r] = gr * a2[r] * (1.0f - cc[r] * cc[r]);
+                p[r] = gr * (cc[r] - zp[r]) * a2[r] * (1.0f - a2[r] * inv_dt);
+                dz[r] = gr * (1.0f - a2[r]);
+            }
+        }
+        if (live) {
+            lwt_tile_store(gt + ldg, ct, p);
+            lwt_tile_store(gt + 2 * ldg, ct, q);
+        }
+        lwt_publish(xf, ct, lane, p);
+        __syncthreads();
+        lwt_gemm<KT, 2>(wA, wB, stream, xf, lane, loff, dy);         // dy += W_g2^T dg2
+        __syncthreads();
+        lwt_publish(xf, ct, lane, q);
+        __syncthreads();
+        lwt_gemm<KT, 3>(wA, wB, stream, xf, lane, loff, dy);         // dy += W_g3^T dg3
+        __syncthreads();
+    }
+}
+
+}  // namespace msmp
+
+using namespace msmp;
+
+static bool lem_wide_train_shape_ok(const char* who, int ninp, int width) {
+    if (!wide_width_ok(who, width)) return false;
+    if (ninp < 1 || ninp > LEM_MAX_INP) {
+        set_error("%s: ninp=%d outside 1..%d", who, ninp, LEM_MAX_INP);
+        return false;
+    }
+    return true;
+}
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+extern "C" int64_t msmp_packed_lem_wide_train_floats(int ninp, int width) {
+    if (!lem_wide_train_shape_ok("msmp_packed_lem_wide_train_floats", ninp, width)) return 0;
+    return lem_wide_train_layout((width + 31) / 32).total;
+}
+
+extern "C" int64_t msmp_packed_lem_wide_bwd_floats(int ninp, int width) {
+    if (!lem_wide_train_shape_ok("msmp_packed_lem_wide_bwd_floats", ninp, width)) return 0;
+    return lem_wide_bwd_floats((width + 31) / 32);
+}
+
+extern "C" int64_t msmp_lem_wide_saved_floats(int64_t n_nodes, int t_len, int width) {
+    if (!wide_width_ok("msmp_lem_wide_saved_floats", width)) return 0;
+    if (n_nodes < 0 || n_nodes >= (1L << 31) || t_len < 1) {
+        set_error("msmp_lem_wide_saved_floats: bad sizes");
+        return 0;
+    }
+    return (int64_t)LWT_PLANES * n_nodes * t_len * (32 * ((width + 31) / 32));
+}
+
+extern "C" int64_t msmp_lem_wide_dg_floats(int64_t n_nodes, int t_len, int width) {
+    if (!wide_width_ok("msmp_lem_wide_dg_floats", width)) return 0;
+    if (n_nodes < 0 || n_nodes >= (1L << 31) || t_len < 1) {
+        set_error("msmp_lem_wide_dg_floats: bad sizes");
+        return 0;
+    }
+    return (int64_t)4 * n_nodes * t_len * (128 * ((width + 127) / 128));
+}
+
+extern "C" int msmp_pack_lem_wide_train_f32(const float* weights, const float* weights_lin_z, const float* bias, const float* bias_lin_z,
+                                            int ninp, int width, float* packed_out, msmp_stream_t stream) {
+    if (!lem_wide_train_shape_ok("msmp_pack_lem_wide_train_f32", ninp, width)) return MSMP_ERR_UNSUPPORTED;
+    MSMP_REQUIRE(weights && weights_lin_z && bias && bias_lin_z && packed_out, MSMP_ERR_ARG, "msmp_pack_lem_wide_train_f32: null pointer");
+    MSMP_REQUIRE(aligned16(packed_out), MSMP_ERR_ARG, "msmp_pack_lem_wide_train_f32: packed_out is not 16-byte aligned");
+    LemWideTrainPackArgs a{weights, weights_lin_z, bias, bias_lin_z, ninp, width, (width + 31) / 32, packed_out};
+    hipLaunchKernelGGL(pack_lem_wide_train_kernel<false>, dim3(2 * a.kt * a.kt), dim3(256), 0, (hipStream_t)stream, a);
+    return check_launch("pack_lem_wide_train_kernel");
+}
+
+extern "C" int msmp_pack_lem_wide_bwd_f32(const float* weights, const float* weights_lin_z, int ninp, int width, float* packed_out,
+                                          msmp_stream_t stream) {
+    if (!lem_wide_train_shape_ok("msmp_pack_lem_wide_bwd_f32", ninp, width)) return MSMP_ERR_UNSUPPORTED;
+    MSMP_REQUIRE(weights && weights_lin_z && packed_out, MSMP_ERR_ARG, "msmp_pack_lem_wide_bwd_f32: null pointer");
+    MSMP_REQUIRE(aligned16(packed_out), MSMP_ERR_ARG, "msmp_pack_lem_wide_bwd_f32: packed_out is not 16-byte aligned");
+    LemWideTrainPackArgs a{weights, weights_lin_z, nullptr, nullptr, ninp, width, (width + 31) / 32, packed_out};
+    hipLaunchKernelGGL(pack_lem_wide_train_kernel<true>, dim3(2 * a.kt * a.kt), dim3(256), 0, (hipStream_t)stream, a);
+    return check_launch("pack_lem_wide_train_kernel");
+}
+
+extern "C" int msmp_lem_train_fwd_wide_f32(const float* xin, int64_t n_nodes, int t_len, int ninp, int width, float dt, const float* packed,
+                                           const float* y0, const float* z0, float* saved, float* y_out, float* z_out, msmp_stream_t stream) {
+    if (!lem_wide_train_shape_ok("msmp_lem_train_fwd_wide_f32", ninp, width)) return MSMP_ERR_UNSUPPORTED;
+    MSMP_REQUIRE(t_len >= 1, MSMP_ERR_ARG, "msmp_lem_train_fwd_wide_f32: t_len=%d < 1", t_len);
+    MSMP_REQUIRE(n_nodes >= 0 && n_nodes < (1L << 31), MSMP_ERR_ARG, "msmp_lem_train_fwd_wide_f32: bad n_nodes");
+    MSMP_REQUIRE(xin && packed && y_out, MSMP_ERR_ARG, "msmp_lem_train_fwd_wide_f32: null pointer");
+    MSMP_REQUIRE((y0 == nullptr) == (z0 == nullptr), MSMP_ERR_ARG, "msmp_lem_train_fwd_wide_f32: give both initial states or none");
+    MSMP_REQUIRE(aligned16(packed) && aligned16(saved), MSMP_ERR_ARG, "msmp_lem_train_fwd_wide_f32: packed / saved not 16-byte aligned");
+    if (n_nodes == 0) return MSMP_OK;
+    const int kt = (width + 31) / 32;
+    const LemWideTrainLayout L = lem_wide_train_layout(kt);
+    LemWideTrainArgs a{xin, (long)n_nodes, t_len, msmp_lem_input_stride(ninp), width, dt, packed + L.rec, packed + L.wx, packed + L.bias,
+                       saved, y0, z0, y_out, z_out};
+    const unsigned grid = (unsigned)((n_nodes + 31) / 32);
+    hipStream_t st = (hipStream_t)stream;
+    dispatch_kt(kt, [&](auto K) {
+        constexpr int KT = decltype(K)::value;
+        hipLaunchKernelGGL((lem_wide_train_fwd_kernel<KT>), dim3(grid), dim3(64 * KT), 0, st, a);
+    });
+    return check_launch("lem_wide_train_fwd_kernel");
+}
+
+extern "C" int msmp_lem_train_bwd_wide_f32(const float* grad_y, const float* saved, const float* y0, const float* z0, int64_t n_nodes, int t_len,
+                                           int width, float dt, const float* packed_bwd, float* dg_out, msmp_stream_t stream) {
+    if (!wide_width_ok("msmp_lem_train_bwd_wide_f32", width)) return MSMP_ERR_UNSUPPORTED;
+    MSMP_REQUIRE(t_len >= 1 && dt != 0.f, MSMP_ERR_ARG, "msmp_lem_train_bwd_wide_f32: t_len=%d < 1 or dt = 0", t_len);
+    MSMP_REQUIRE(n_nodes >= 0 && n_nodes < (1L << 31), MSMP_ERR_ARG, "msmp_lem_train_bwd_wide_f32: bad n_nodes");
+    MSMP_REQUIRE(grad_y && saved && packed_bwd && dg_out, MSMP_ERR_ARG, "msmp_lem_train_bwd_wide_f32: null pointer");
+    MSMP_REQUIRE((y0 == nullptr) == (z0 == nullptr), MSMP_ERR_ARG, "msmp_lem_train_bwd_wide_f32: give both initial states or none");
+    MSMP_REQUIRE(aligned16(packed_bwd) && aligned16(saved) && aligned16(dg_out), MSMP_ERR_ARG,
+                 "msmp_lem_train_bwd_wide_f32: packed_bwd / saved / dg_out not 16-byte aligned");
+    if (n_nodes == 0) return MSMP_OK;
+    const int kt = (width + 31) / 32;
+    LemWideBwdArgs a{grad_y, saved, (long)n_nodes, t_len, width, 128 * ((width + 127) / 128), dt, packed_bwd, dg_out, z0};
+    const unsigned grid = (unsigned)((n_nodes + 31) / 32);
+    hipStream_t st = (hipStream_t)stream;
+    dispatch_kt(kt, [&](auto K) {
+        constexpr int KT = decltype(K)::value;
+        hipLaunchKernelGGL((lem_wide_bptt_kernel<KT>), dim3(grid), dim3(64 * KT), 0, st, a);
+    });
+    return check_launch("lem_wide_bptt_kernel");
+}

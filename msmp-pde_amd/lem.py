@@ -28,6 +28,7 @@ class LEMcuda(nn.Module):
         self.bias = nn.Parameter(torch.empty(3 * nhid, dtype=torch.float32))
         self.bias_lin_z = nn.Parameter(torch.empty(nhid, dtype=torch.float32))
         self._wide_blob = PackedCache()
+        self._wide_train_blob = PackedCache()
         self.reset_parameters()
 
     def _pack_wide(self):
@@ -44,6 +45,28 @@ class LEMcuda(nn.Module):
             check(L.msmp_pack_lem_wide_f32(*[ptr(t) for t in f], self.ninp, self.nhid, ptr(blob), current_stream()), 'msmp_pack_lem_wide_f32')
             return blob
         return self._wide_blob.get(ps, build)
+
+    def _pack_wide_train(self):
+        """The forward blob of msmp_lem_train_fwd_wide_f32 (bf16x3 fragments), cached like _pack_wide."""
+        ps = [self.weights, self.weights_lin_z, self.bias, self.bias_lin_z]
+
+        def build():
+            L = lib()
+            n_floats = L.msmp_packed_lem_wide_train_floats(self.ninp, self.nhid)
+            if n_floats <= 0:
+                check(MSMP_ERR_UNSUPPORTED, 'msmp_packed_lem_wide_train_floats')
+            blob = torch.empty(n_floats, dtype=torch.float32, device=ps[0].device)
+            f = [p.detach().to(torch.float32).contiguous() for p in ps]
+            check(L.msmp_pack_lem_wide_train_f32(*[ptr(t) for t in f], self.ninp, self.nhid, ptr(blob), current_stream()), 'msmp_pack_lem_wide_train_f32')
+            return blob
+        return self._wide_train_blob.get(ps, build)
+
+    def wide_train_selected(self, xin):
+        """True where a forward under autograd runs on the width-generic training kernels (_LEMWideTrainFunction): grad enabled, some
+        parameter requires grad, fp32 parameters and inputs on the GPU, at least one node, msmp_tune "lem_wide_train" not 0."""
+        return (torch.is_grad_enabled() and xin.is_cuda and xin.dtype == torch.float32 and xin.shape[0] > 0 and self.wide_kernel_exists()
+                and all(p.dtype == torch.float32 and p.is_cuda for p in self.parameters()) and any(p.requires_grad for p in self.parameters())
+                and lib().msmp_tune_query(b'lem_wide_train') != 0)
 
     def wide_kernel_exists(self):
         """True at the sizes msmp_lem_encoder_wide_f32 takes."""
@@ -170,10 +193,67 @@ class _LEMTrainFunction(torch.autograd.Function):
         return None, None, d_w.to(weights.dtype), g[6].to(weights_lin_z.dtype), d_b, g[7], None, None
 
 
+def _wide_train_forward(rnn, x, y0, z0, saved):
+    """msmp_lem_train_fwd_wide_f32: the fp32-exact recurrence at any width from the states (y0, z0) (None = zeros) -> (y_T, z_T)."""
+    n, t_len = x.shape[0], x.shape[1]
+    out = torch.empty(n, rnn.nhid, dtype=torch.float32, device=x.device)
+    z_out = torch.empty_like(out)
+    check(lib().msmp_lem_train_fwd_wide_f32(ptr(x), n, t_len, rnn.ninp, rnn.nhid, rnn.dt, ptr(rnn._pack_wide_train()), ptr(y0), ptr(z0),
+                                            ptr(saved), ptr(out), ptr(z_out), current_stream()), 'msmp_lem_train_fwd_wide_f32')
+    return out, z_out
+
+
+class _LEMWideTrainFunction(torch.autograd.Function):
+    """_LEMTrainFunction at any hidden width 1..256 (the GLU classes: 164): forward = msmp_lem_train_fwd_wide_f32, backward =
+    msmp_lem_train_bwd_wide_f32 followed by ONE msmp_grad_weights_cat_f32 call whose jobs are the 128-column blocks of the four gates
+    of dG (at most 8).  Allocates through torch only and never synchronises (hipGraph capture).  No gradient for the step inputs or the
+    initial states, as at 128."""
+
+    @staticmethod
+    def forward(ctx, rnn, xin, weights, weights_lin_z, bias, bias_lin_z, y0=None, z0=None):
+        x = _padded_inputs(xin)
+        n, t_len, _ = xin.shape
+        saved = torch.empty(lib().msmp_lem_wide_saved_floats(n, t_len, rnn.nhid), dtype=torch.float32, device=x.device)
+        y0, z0 = _state(y0), _state(z0)
+        out, z_out = _wide_train_forward(rnn, x, y0, z0, saved)
+        ctx.save_for_backward(x, saved, weights, weights_lin_z, *([y0, z0] if y0 is not None else []))
+        ctx.dt, ctx.ninp = rnn.dt, rnn.ninp
+        ctx.mark_non_differentiable(z_out)
+        return out, z_out
+
+    @staticmethod
+    def backward(ctx, grad_y, _grad_z=None):
+        L = lib()
+        x, saved, weights, weights_lin_z, *states = ctx.saved_tensors
+        y0, z0 = states if states else (None, None)
+        n, t_len, stride = x.shape
+        nh, ninp = weights_lin_z.shape[0], ctx.ninp
+        wp, ldg, nblk = 32 * ((nh + 31) // 32), 128 * ((nh + 127) // 128), (nh + 127) // 128
+        blob = torch.empty(L.msmp_packed_lem_wide_bwd_floats(ninp, nh), dtype=torch.float32, device=x.device)
+        w, wz = (p.detach().to(torch.float32).contiguous() for p in (weights, weights_lin_z))
+        check(L.msmp_pack_lem_wide_bwd_f32(ptr(w), ptr(wz), ninp, nh, ptr(blob), current_stream()), 'msmp_pack_lem_wide_bwd_f32')
+        dg = torch.empty(n * t_len, 4 * ldg, dtype=torch.float32, device=x.device)      # every element is written by the kernel
+        g = grad_y.to(torch.float32).contiguous()
+        check(L.msmp_lem_train_bwd_wide_f32(ptr(g), ptr(saved), ptr(y0), ptr(z0), n, t_len, nh, ctx.dt, ptr(blob), ptr(dg), current_stream()),
+              'msmp_lem_train_bwd_wide_f32')
+        planes = saved.view(6, n * t_len, wp)
+        xs = x.view(n * t_len, stride)[:, :ninp]
+        y_prev, z_new = planes[4][:, :nh], planes[5][:, :nh]
+        from .autograd import grad_weights
+        jobs = [(dg[:, gate * ldg + 128 * j:gate * ldg + 128 * (j + 1)], z_new if gate == 3 else y_prev, xs) for gate in range(4) for j in range(nblk)]
+        r = grad_weights(jobs)
+        gate_w = [torch.cat(r[2 * nblk * gate:2 * nblk * (gate + 1):2], 0)[:nh] for gate in range(4)]       # rows >= width of a block: zero columns of dG
+        gate_b = [torch.cat(r[2 * nblk * gate + 1:2 * nblk * (gate + 1):2], 0)[:nh] for gate in range(4)]
+        return (None, None, torch.cat(gate_w[:3], 0).to(weights.dtype), gate_w[3].to(weights_lin_z.dtype), torch.cat(gate_b[:3], 0), gate_b[3],
+                None, None)
+
+
 class LEM(nn.Module):
     """experiments/models_gnn.py:333-342: returns all_y[-1].
 
-    `forward` is the differentiable path: the HIP training kernels (_LEMTrainFunction).  There is NO CPU path: host tensors
+    `forward` is the differentiable path: the HIP training kernels (_LEMTrainFunction at width 128; at any other width
+    _LEMWideTrainFunction while msmp_tune "lem_wide_train" is not 0, some LEM parameter requires grad and module and inputs are fp32, else
+    the PyTorch-ROCm restatement).  There is NO CPU path: host tensors
     raise.  TRAIN_KERNELS = False is a validation aid only (scripts/train_soak.py, scripts/train_step_time.py): it routes GPU
     tensors through the PyTorch-ROCm restatement `LEMcuda.forward`, which the tests also call directly in float64 as the
     reference of the kernels.  `encode` /
@@ -195,9 +275,12 @@ class LEM(nn.Module):
         """Same with node-major step inputs xin [N, T, ninp] (the layout the kernels read)."""
         if not xin.is_cuda:
             raise RuntimeError('LEM needs CUDA tensors; there is no CPU fallback')
-        if self.nhid != 128:            # the GLU classes (164 hidden units): no grad = the width-generic HIP kernel, else the PyTorch-ROCm restatement of the cell
+        if self.nhid != 128:            # the GLU classes (164 hidden units): no grad = the width-generic HIP kernel, training = its bf16x3 pair, else the PyTorch-ROCm restatement of the cell
             if not torch.is_grad_enabled() and xin.shape[0] > 0 and self.rnn.weights.dtype == torch.float32 and self.rnn.wide_kernel_selected():
                 return self.rnn.forward_wide(xin)[0]
+            if self.TRAIN_KERNELS and self.rnn.wide_train_selected(xin):
+                r = self.rnn
+                return _LEMWideTrainFunction.apply(r, xin, r.weights, r.weights_lin_z, r.bias, r.bias_lin_z)[0]
             return self.rnn(xin.permute(1, 0, 2).contiguous().to(self.rnn.weights.dtype))
         if not self.TRAIN_KERNELS:
             return self.rnn(xin.permute(1, 0, 2).contiguous())
@@ -256,7 +339,8 @@ class LEMS(LEM):
     the next call.  At width 128 it runs on the exact-fp32 recurrence kernel (msmp_lem_train_fwd_f32; with autograd its BPTT pair), which
     takes initial states; the weight-stationary inference kernel starts from zeros and is not used here.  At any other width: without
     grad LEMcuda.forward's inference branch (msmp_lem_encoder_wide_f32, or the GEMM loop under msmp_tune "lem_wide" 0 / exact fp32), with
-    grad the PyTorch-ROCm restatement, both with the carried states."""
+    grad the width-generic training pair (_LEMWideTrainFunction: msmp_lem_train_fwd_wide_f32 / _bwd_wide_f32, which take initial states) or,
+    under msmp_tune "lem_wide_train" 0, TRAIN_KERNELS = False or in float64, the PyTorch-ROCm restatement; all with the carried states."""
 
     def __init__(self, ninp, nhid, dt=1.):
         super().__init__(ninp, nhid, dt)
@@ -274,7 +358,10 @@ class LEMS(LEM):
         if not xin.is_cuda:
             raise RuntimeError('LEMS needs CUDA tensors (HIP path only, no CPU fallback)')
         if self.nhid != 128:
-            y, z = r(xin.permute(1, 0, 2).contiguous().to(r.weights.dtype), None if y0 is None else (y0, z0), return_state=True)
+            if self.TRAIN_KERNELS and r.wide_train_selected(xin):
+                y, z = _LEMWideTrainFunction.apply(r, xin, r.weights, r.weights_lin_z, r.bias, r.bias_lin_z, y0, z0)
+            else:
+                y, z = r(xin.permute(1, 0, 2).contiguous().to(r.weights.dtype), None if y0 is None else (y0, z0), return_state=True)
         elif torch.is_grad_enabled() and any(p.requires_grad for p in r.parameters()):
             if self.TRAIN_KERNELS:
                 y, z = _LEMTrainFunction.apply(self, xin, r.weights, r.weights_lin_z, r.bias, r.bias_lin_z, y0, z0)
