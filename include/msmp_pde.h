@@ -109,6 +109,10 @@ int msmp_last_status(int* flags_out, int reset);
  *             a gated pair) as one msmp_wide_node_proj_f32 launch; 0 (default): a concatenation [h | u | pos | vars] and two msmp_linear_f32 per head
  *             (the entry itself does not read the key).  The host takes the fused launch only while "wide_msg", "split" and "lem_wide" are 1
  *             as well, so each of those keeps selecting the path it selected before this kernel.
+ *   "wide_bwd" 1 (default): under autograd the host's layer at widths other than 128 runs the width-generic HIP forward (saving only the
+ *             layer inputs) and one msmp_wide_layer_bwd_f32 call per layer / gated pair as its backward; 0: PyTorch ops differentiated by
+ *             torch.autograd (the entry itself does not read the key; any value other than 0 selects the kernels).  float64 inputs and sizes the
+ *             entry refuses by value keep the PyTorch ops.  Measured: DESIGN.md section 4.23.
  *   "wide_dec" 1 (default): the host's no-grad forward of the GLU classes ends in one msmp_decoder_gated_f32 / msmp_decoder2d_gated_f32
  *             launch (2-D: after double_mlp as one msmp_linear_f32); 0: the decoder's PyTorch ops (the entries themselves do not read the
  *             key; any value other than 0 selects the launch).  The host takes the launch only while "wide_msg", "split" and "lem_wide"
@@ -653,6 +657,23 @@ int msmp_pack_wide_proj_f32(const float* w1, const float* b1, int width, int tw,
  * negative sizes; n_nodes == 0 is a no-op.  Allocates nothing and never synchronises. */
 int msmp_wide_node_proj_f32(const float* h, const float* feat, int64_t n_nodes, int tw, int nv, int width, int ld, const float* packed_main,
                             const float* packed_gate, float* p_main, float* q_main, float* p_gate, float* q_gate, msmp_stream_t stream);
+/* The backward of one GNN_LayerLin, or of a gated pair of them, at any hidden width 1..256 in one call: the width-generic counterpart of
+ * msmp_mp_layer_bwd_f32, same meaning (experiments/models_gnn.py:88-149, 1486-1489; params_gate == grads_gate == NULL: a single layer).
+ * grad_out, h, dh_out [N, ld] with ld = 128 ceil(width / 128), 16-byte aligned; the padding columns width .. ld - 1 are zero on input and
+ * written as zero.  params_* / grads_*: arrays of 8 device pointers in the reference's [out, in] layouts with out = width (message_net_1.0.weight
+ * [width, 2 width + tw + 1 + nv], ..., update_net_2.0.bias [width]); u, pos, vars carry no gradient.  ONE algorithm: message_net_1 factorised
+ * through per-node projections (nothing edge-sized of width 2 width + tw + 1 + nv), fp32-exact bf16x3 row GEMMs, sums in fixed orders, batched
+ * fp32-exact weight gradients; no atomics, no memset, no library GEMM: two calls on the same inputs give the same bits.  src_rowptr [N+1] /
+ * src_perm [E] (the CSR edge ids regrouped by source, ascending inside a source) are REQUIRED when n_edges > 0 (MSMP_ERR_ARG without).
+ * MSMP_ERR_UNSUPPORTED (nothing launched; the workspace query returns 0) for a width outside 1..256, tw + 1 + nv > 128 or nv > MSMP_MAX_VARS;
+ * MSMP_ERR_ARG for a null or misaligned pointer, ld other than 128 ceil(width / 128) or bad sizes.  Allocates nothing, never synchronises. */
+size_t msmp_wide_layer_bwd_workspace_bytes(int64_t n_nodes, int64_t n_edges, int tw, int nv, int width, int gated);
+int msmp_wide_layer_bwd_f32(const float* grad_out, const float* h, const float* u, const float* pos, const float* vars,
+                            const int32_t* rowptr, const int32_t* col, const int32_t* tgt, const int32_t* src_rowptr,
+                            const int32_t* src_perm, const int32_t* graph_ptr, int64_t n_nodes, int64_t n_edges, int64_t n_graphs,
+                            int tw, int nv, int width, int ld, const float* const* params_main, const float* const* params_gate,
+                            float eps, float* dh_out, float* const* grads_main, float* const* grads_gate, void* workspace,
+                            size_t workspace_bytes, msmp_stream_t stream);
 /* gate_pre == NULL: out = InstanceNorm(main_pre); else out = (1 - tau) h + tau Swish(IN(main_pre)), tau = sigmoid(IN(gate_pre)) */
 int msmp_wide_norm_blend_f32(const float* h, const float* gate_pre, const float* main_pre, const int32_t* graph_ptr, int64_t n_graphs,
                              int width, int ld, float eps, float* out, msmp_stream_t stream);

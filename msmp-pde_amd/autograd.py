@@ -8,11 +8,12 @@ else HIP kernels too (edge concat, bias + Swish, mean-backward + Swish', Instanc
 the batched weight-gradient kernel).  `EXPLICIT_BACKWARD = 1` runs the same algorithm orchestrated from Python (library GEMMs
 through torch, ~65 ops per pair), `0` differentiates a PyTorch restatement with torch.autograd (~190 ops): kept for cross-checks.  Nothing runs on
 the CPU and nothing here is used by the inference / rollout path.  The math is that of experiments/models_gnn.py:61-149
-and :1204-1207."""
+and :1204-1207.  At a hidden width other than 128 (the GLU classes: 164) the backward is msmp_wide_layer_bwd_f32
+(wide_layer_bwd_kernel.hip): the same algorithm in its factorised form only, at any width up to 256."""
 import torch
 import torch.nn.functional as F
 
-from ._lib import lib, check, ptr, current_stream
+from ._lib import lib, check, ptr, current_stream, MsmpError
 
 # 2: the whole layer backward behind the C-ABI (msmp_mp_layer_bwd_f32, launches issued from native code);
 # 1: the same algorithm orchestrated from Python (library GEMMs through torch); 0: torch.autograd over a restatement.
@@ -43,6 +44,46 @@ def layer_backward_native(gout, h, u, pos, variables, gs, params, mode_lin, gate
                                   1 if (mode_lin or gated) else 0, eps, ptr(dh), arr(grads[:8]), arr(grads[8:]) if gated else None,
                                   ptr(ws), ws.numel(), current_stream()), 'msmp_mp_layer_bwd_f32')
     return dh, grads
+
+
+_wide_bwd_ws = {}
+
+
+def wide_layer_bwd_taken(n, e, tw, nv, width, gated):
+    """True where msmp_wide_layer_bwd_f32 takes these sizes (its workspace query is 0 for the sizes it refuses by value)."""
+    return lib().msmp_wide_layer_bwd_workspace_bytes(n, e, tw, nv, width, int(gated)) > 0
+
+
+def layer_backward_wide_native(gout, h, u, pos, variables, gs, params, gated, eps):
+    """layer_backward_native at a hidden width other than 128: dL/dh [N, W] and the parameter gradients of one GNN_LayerLin / gated pair
+    through msmp_wide_layer_bwd_f32 (rows padded to wide.row_stride(W) columns on the way in, cut on the way out)."""
+    import ctypes
+    from .wide import row_stride, _entry_taken
+    L = lib()
+    dev = h.device
+    n, W, e, tw, nv = h.shape[0], h.shape[1], gs.n_edges, u.shape[1], variables.shape[1]
+    ld = row_stride(W)
+    f32 = lambda t: t.detach() if (t.dtype == torch.float32 and t.is_contiguous()) else t.detach().to(torch.float32).contiguous()
+    ps = [f32(q) for q in params]
+    grads = [torch.empty(q.shape, dtype=torch.float32, device=dev) for q in ps]
+    hp = torch.zeros(n, ld, dtype=torch.float32, device=dev)
+    hp[:, :W] = h
+    g = torch.zeros(n, ld, dtype=torch.float32, device=dev)
+    g[:, :W] = gout
+    dh = torch.empty(n, ld, dtype=torch.float32, device=dev)
+    need = L.msmp_wide_layer_bwd_workspace_bytes(n, e, tw, nv, W, int(gated))
+    ws = _wide_bwd_ws.get(dev)                  # grow-only scratch per device, its own: the 128-wide backward keeps _bwd_ws
+    if ws is None or ws.numel() < need:
+        ws = _wide_bwd_ws[dev] = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    arr = lambda ts: (ctypes.c_void_p * 8)(*[t.data_ptr() for t in ts])
+    perm32, src_rowptr = gs.by_source32() if e else (None, None)
+    rc = L.msmp_wide_layer_bwd_f32(ptr(g), ptr(hp), ptr(f32(u)), ptr(f32(pos)), ptr(f32(variables)), ptr(gs.rowptr), ptr(gs.col), ptr(gs.tgt),
+                                   ptr(src_rowptr), ptr(perm32), ptr(gs.graph_ptr), n, e, gs.n_graphs, tw, nv, W, ld, arr(ps[:8]),
+                                   arr(ps[8:]) if gated else None, eps, ptr(dh), arr(grads[:8]), arr(grads[8:]) if gated else None,
+                                   ptr(ws), ws.numel(), current_stream())
+    if not _entry_taken('msmp_wide_layer_bwd_f32', rc):
+        raise MsmpError('msmp_wide_layer_bwd_f32 refused sizes its workspace query took: ' + L.msmp_last_error().decode())
+    return dh[:, :W].contiguous(), grads
 
 
 def _swish(x):
@@ -215,6 +256,10 @@ class MPLayerFunction(torch.autograd.Function):
     def backward(ctx, gout):
         h, u, pos, variables, *params = ctx.saved_tensors
         gs, mode, gated, eps = ctx.meta
+        if h.shape[1] != 128:                   # the width-generic layer (GNN_LayerLin heads only): one algorithm, msmp_wide_layer_bwd_f32
+            with torch.no_grad():
+                dh, grads = layer_backward_wide_native(gout, h, u, pos.reshape(-1), variables, gs, params, gated, eps)
+            return (dh, None, None, None, None, None, None, None, None) + tuple(grads)
         if EXPLICIT_BACKWARD:
             with torch.no_grad():
                 fn = layer_backward_native if EXPLICIT_BACKWARD == 2 else layer_backward_explicit

@@ -30,6 +30,7 @@ SOURCES = {  # file -> extra flags
     'train_kernels.hip': [],
     'mlp2_kernel.hip': [],
     'wide_kernels.hip': [],
+    'wide_layer_bwd_kernel.hip': [],
     'decoder_kernel.hip': [],
     'graph_kernels.hip': ['-ffp-contract=off'],   # float64 distance compares must round like the host's
 }

@@ -477,6 +477,7 @@ static TuneRow g_tune[] = {
     {"wide_msg", 1, ON_OFF},    // 0: the host layer keeps gather + row GEMM + scatter at widths other than 128
     {"wide_tail", 0, ON_OFF},    // 1: the host layer takes msmp_wide_node_tail_f32 at widths other than 128 (wide_node_tail_kernel.hip)
     {"wide_proj", 0, ON_OFF},    // 1: the host layer takes msmp_wide_node_proj_f32 at widths other than 128 (wide_node_proj_kernel.hip)
+    {"wide_bwd", 1, ANY_INT},    // != 0: under autograd the host's layer at widths other than 128 takes msmp_wide_layer_bwd_f32 (wide_layer_bwd_kernel.hip); 0: PyTorch ops
     {"wide_dec", 1, ANY_INT},    // != 0: the host ends the GLU classes' forward in msmp_decoder_gated_f32 / msmp_decoder2d_gated_f32 (decoder_kernel.hip)
 };
 #undef ANY_INT

@@ -9,6 +9,7 @@
 // All fp32, HBM-bound, one pass per tensor where the per-graph statistics allow it.
 #include "graph_norm.h"
 #include "mfma_tiles.h"
+#include "train_internal.h"
 
 namespace msmp {
 
@@ -30,11 +31,6 @@ __global__ __launch_bounds__(256) void edge_concat_kernel(const float* __restric
             else row[2 * H + k] = vars[(size_t)i * nv + (k - tw - 1)];
         }
     }
-}
-
-__device__ __forceinline__ float dswish(float x) {        // d/dx x sigmoid(x)
-    const float s = sigmoidf_(x);
-    return s * (1.0f + x * (1.0f - s));
 }
 
 // da2[e] = dagg[tgt[e]] / max(deg, 1) * Swish'(a2[e]);  thread = (edge, 16-B channel group)
@@ -195,7 +191,6 @@ extern "C" int msmp_gate_blend_bwd_f32(const float* grad_out, const float* h, co
 // ----------------------------------------------------------------------------------------------
 namespace msmp {
 
-constexpr int GW_MAX_JOBS = 10;
 constexpr int GW_MAX_UNITS = 2 * GW_MAX_JOBS;       // a job of more than 160 columns is two column groups
 struct GradWeightJob {
     const float* a;      // [rows, lda], columns 0..127 used
@@ -413,10 +408,9 @@ extern "C" int64_t msmp_grad_weights_workspace_floats(int n_jobs, const int64_t*
 
 namespace msmp {
 // launches of msmp_grad_weights_f32 on validated arguments (also used by the layer backward below)
-static int launch_grad_weights(int n_jobs, const float* const* a, const float* const* b, const int64_t* rows, const int* lda,
-                               const int* ldb, const int* k2, float* const* out_w, float* const* out_b, float* workspace,
-                               int64_t workspace_floats, hipStream_t stream, const float* const* b2 = nullptr, const int* ldb2 = nullptr,
-                               const int* ksplit = nullptr) {
+int launch_grad_weights(int n_jobs, const float* const* a, const float* const* b, const int64_t* rows, const int* lda,
+                        const int* ldb, const int* k2, float* const* out_w, float* const* out_b, float* workspace,
+                        int64_t workspace_floats, hipStream_t stream, const float* const* b2, const int* ldb2, const int* ksplit) {
     GradWeightArgs args;
     args.n_jobs = n_jobs;
     int64_t used = 0;
@@ -622,7 +616,7 @@ __global__ __launch_bounds__(256) void scatter_source_sorted_kernel(float* __res
     }
 }
 
-static unsigned grid_for(long work_items) {
+unsigned grid_for(long work_items) {
     const long b = (work_items + 255) / 256;
     return (unsigned)(b < 1 ? 1 : b > 32768 ? 32768 : b);
 }
@@ -750,22 +744,7 @@ static void carve(float*& p, long n, long e, int ld_e, int ld_n, int ldf, HeadBu
 //   EPI 4: Swish(acc + bias) -> out0                         (msmp_linear_swish_f32: the *2D classes' double_mlp)
 //   EPI 5: out0 += acc                                       (node-level data gradient of the factorised message_net_1)
 // ----------------------------------------------------------------------------------------------------------------------
-constexpr int RG_CHUNK_U4 = 2 * 4 * 3 * 64;            // 16-byte fragments per 32-k chunk: [s][T][plane][lane]
-constexpr int RG_CHUNK_FLOATS = RG_CHUNK_U4 * 4;       // 24 KB
-
-struct RgPackJob {
-    const float* w;      // row-major, row stride ldw
-    u32x4* out;          // n_chunks * RG_CHUNK_U4 fragments
-    int ldw, K, n_chunks, col0, transposed, n_rows;     // rows (output channels) >= n_rows read as zero (forward form; msmp_linear_f32's last group)
-    // transposed = 0: W_eff[o][k] = w[(col0 + o) * ldw + k]   (forward form: rows of w are output channels)
-    // transposed = 1: W_eff[o][k] = w[k * ldw + col0 + o]     (data-gradient form: the reduction runs over w's rows)
-    int first_block;
-};
-constexpr int RG_MAX_PACK = 24;
-struct RgPackArgs {
-    RgPackJob job[RG_MAX_PACK];
-    int n_jobs;
-};
+// (RG_CHUNK_U4, RgPackJob, RgPackArgs: train_internal.h)
 __global__ __launch_bounds__(256) void rg_pack_kernel(RgPackArgs a) {
     int ji = 0;
     for (int i = 1; i < a.n_jobs; ++i)
@@ -982,8 +961,8 @@ __global__ __launch_bounds__(256) void rows_gemm_small_kernel(RgArgs a) {
 
 constexpr long RG_SMALL_ROWS = 32768;      // below this many rows the 32-row workgroups fill the chip better (294 x 4 waves at E = 9 408)
 
-static int rows_gemm(int epi, const float* x, int ldx, long rows, int K, const u32x4* wfrag, const float* bias, const float* aux, float* out0,
-                     int ld0, float* out1, hipStream_t st) {
+int rows_gemm(int epi, const float* x, int ldx, long rows, int K, const u32x4* wfrag, const float* bias, const float* aux, float* out0,
+              int ld0, float* out1, hipStream_t st) {
     RgArgs a{x, wfrag, bias, aux, out0, out1, rows, ldx, K, (K + 31) / 32, ld0};
     if (rows < RG_SMALL_ROWS) {
         const dim3 gs((unsigned)((rows + 31) / 32));
@@ -1024,11 +1003,17 @@ static void carve_frags(u32x4*& p, int kmsg, int kupd, int ldf, HeadFrags& f) {
     f.w4t = take(4); f.w3t[0] = take(4); f.w3t[1] = take(4); f.w2t = take(4); f.w1t[0] = take(4); f.w1t[1] = take(4);
     f.wp = take(ldf / 32); f.wq = take(ldf / 32);
 }
-static void add_pack(RgPackArgs& a, int& blocks, const float* w, int ldw, int K, int col0, int transposed, u32x4* out) {
+void add_pack(RgPackArgs& a, int& blocks, const float* w, int ldw, int K, int col0, int transposed, u32x4* out) {
     RgPackJob& j = a.job[a.n_jobs++];
     j.w = w; j.out = out; j.ldw = ldw; j.K = K; j.n_chunks = (K + 31) / 32; j.col0 = col0; j.transposed = transposed; j.first_block = blocks;
     j.n_rows = 0x7fffffff;
     blocks += (j.n_chunks * 512 + 255) / 256;
+}
+// the split launch for the jobs collected by add_pack (for callers outside this file: train_internal.h)
+int launch_rg_pack(RgPackArgs& a, int blocks, hipStream_t st) {
+    for (int i = a.n_jobs; i < RG_MAX_PACK; ++i) a.job[i] = a.job[0];
+    hipLaunchKernelGGL(rg_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
+    return check_launch("rg_pack_kernel");
 }
 static int pack_head_frags(const float* const* p, int kmsg, int kupd, const HeadFrags& f, RgPackArgs& a, int& blocks, const float* wp, const float* wq,
                            int ldf) {

@@ -189,6 +189,14 @@ def mp_layer(h, u, pos_x, variables, structure, main, gate=None, eps=1e-5, dense
     need_grad = torch.is_grad_enabled() and (h.requires_grad or any(p.requires_grad for p in main._params8()))
     if main.wide:
         if need_grad:
+            # msmp_tune("wide_bwd") != 0: HIP forward (saving only the layer inputs) + one msmp_wide_layer_bwd_f32 call, as at width 128;
+            # float64 inputs and sizes the entry refuses by value keep the PyTorch ops
+            if h.dtype == torch.float32 and main.MODE == _lib.MSMP_LAYER_LIN and lib().msmp_tune_query(b'wide_bwd'):
+                from .autograd import MPLayerFunction, wide_layer_bwd_taken
+                if wide_layer_bwd_taken(h.shape[0], gs.n_edges, u.shape[1], variables.shape[1], h.shape[1], gate is not None):
+                    params = list(main._params8()) + (list(gate._params8()) if gate is not None else [])
+                    return MPLayerFunction.apply(h.contiguous(), _f32c(u), _f32c(pos_x).reshape(-1), _f32c(variables), gs, main, gate, eps,
+                                                 _mp_layer_wide, *params)
             return _mp_layer_wide_autograd(h, u.to(h.dtype), pos_x, variables.to(h.dtype), gs, main, gate, eps)
         return _mp_layer_wide(_f32c(h), _f32c(u), _f32c(pos_x).reshape(-1), _f32c(variables), gs, main, gate, eps, feat)
     hd, u, pos_x, variables = _f32c(h), _f32c(u), _f32c(pos_x).reshape(-1), _f32c(variables)

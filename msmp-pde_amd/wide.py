@@ -200,8 +200,9 @@ def _mp_layer_wide(h, u, pos_x, variables, gs, main, gate, eps, feat=None):
 
 
 def _mp_layer_wide_autograd(h, u, pos_x, variables, gs, main, gate, eps):
-    """The same layer as differentiable PyTorch-ROCm ops (training of the GLU ablation classes): gathers, F.linear, index_add_
-    mean, InstanceNorm and the blend, formula by formula as experiments/models_gnn.py:124-149, 1486-1489."""
+    """The same layer as differentiable PyTorch-ROCm ops: gathers, F.linear, index_add_ mean, InstanceNorm and the blend, formula by
+    formula as experiments/models_gnn.py:124-149, 1486-1489.  What layers.mp_layer takes under autograd with msmp_tune("wide_bwd") at 0,
+    for float64 inputs and for sizes msmp_wide_layer_bwd_f32 refuses; otherwise training runs _mp_layer_wide + that entry."""
     i, j = gs.tgt_long, gs.col_long
     n = h.shape[0]
     deg = (gs.rowptr[1:] - gs.rowptr[:-1]).clamp(min=1).to(h.dtype)[:, None]

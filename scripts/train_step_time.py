@@ -5,7 +5,8 @@ on the HIP forward / native backward path, E2, reference batch size 16 and large
     --model NAME          one model of msmp_pde_amd.MODEL_NAMES (repeatable; default MSMP-PDE, Gated, MP-PDE)
     --batches 16,512      batch sizes (default 16,128,512)
     --warmup W --iters N  untimed and timed iterations per (model, batch) (default 4 and 5)
-    --tune KEY=VALUE      an msmp_tune switch for the whole process (repeatable), e.g. --tune lem_wide_train=1"""
+    --tune KEY=VALUE      an msmp_tune switch for the whole process (repeatable), e.g. --tune lem_wide_train=1
+    --exp NAME            the experiment of msmp_pde_amd.synthetic.EXPERIMENTS (default E2; MSWG3 for the *2D classes)"""
 import argparse
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -21,6 +22,7 @@ ap.add_argument('--warmup', type=int, default=4)
 ap.add_argument('--iters', type=int, default=5)
 ap.add_argument('--tune', action='append', default=[])
 ap.add_argument('--torch-adamw', action='store_true')
+ap.add_argument('--exp', default='E2')
 args = ap.parse_args()
 for kv in args.tune:
     key, value = kv.split('=')
@@ -31,8 +33,8 @@ for name, lem_kernels in variants:
     LEM.TRAIN_KERNELS = lem_kernels
     for bsz in [int(b) for b in args.batches.split(',')]:
         torch.manual_seed(0)
-        case = make_case('E2', bsz, seed=1, device='cuda', dtype=torch.float32)
-        model = mp.MODEL_NAMES[name](case.pde, time_window=25, eq_variables=EXPERIMENTS['E2'], hidden_layer=6).cuda().train()
+        case = make_case(args.exp, bsz, seed=1, device='cuda', dtype=torch.float32)
+        model = mp.MODEL_NAMES[name](case.pde, time_window=25, eq_variables=case.eqv, hidden_layer=6).cuda().train()
         opt = (torch.optim.AdamW(model.parameters(), lr=1e-4, weight_decay=1e-8, fused=True) if TORCH_ADAMW
                else mp.optim.AdamW(model.parameters(), lr=1e-4, weight_decay=1e-8))
         steps = [60] * bsz
