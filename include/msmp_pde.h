@@ -117,6 +117,11 @@ int msmp_last_status(int* flags_out, int reset);
  *             launch (2-D: after double_mlp as one msmp_linear_f32); 0: the decoder's PyTorch ops (the entries themselves do not read the
  *             key; any value other than 0 selects the launch).  The host takes the launch only while "wide_msg", "split" and "lem_wide"
  *             are 1 as well, so each of those keeps selecting the path it selected before these kernels.
+ *   "dec_bwd" 1 (default): under autograd the host's CNN decoder of every solver class is msmp_decoder*_train_fwd_f32 forward and one
+ *             msmp_decoder*_bwd_f32 call backward; 0: PyTorch-ROCm ops (Toeplitz GEMMs) differentiated by torch.autograd (the entries
+ *             themselves do not read the key; any value other than 0 selects the kernels).  The GLU classes take them only while "wide_msg",
+ *             "split" and "lem_wide" are 1 as well.  CPU tensors, float64, a `u` that requires grad and sizes the entries refuse by value
+ *             keep the PyTorch ops.  Measured: DESIGN.md section 4.24.
  *   "tile_arith" 1 (default): ranged tiles take their node rows by arithmetic on tile_halo; 0: always through the node list.
  *   "tile_align" 0 (default): the host cuts the node tiles of a batch of identical graphs at graph boundaries only where tile_nodes divides
  *             the graph size; 1: also where it does not (bitwise graph-order / sharding equivariance on knn graphs, 11-20 % more tiles
@@ -388,6 +393,54 @@ int msmp_decoder_gated_f32(const float* h, int ld, const float* u, int64_t n_nod
 int msmp_decoder2d_gated_f32(const float* hd, int ld, const float* u, int64_t n_nodes, int width, int tw, const float* gate_w1,
                              const float* gate_b1, const float* gate_w2, const float* gate_b2, const float* diff_w1, const float* diff_b1,
                              const float* diff_w2, const float* diff_b2, float dt, float* out, msmp_stream_t stream);
+
+/* The decoders under autograd: forward-for-training entries and one backward call each.
+ * msmp_decoder*_train_fwd_f32 have the prototypes, the kernels and the bits of their inference twins above; they only stay outside the
+ * event bracket of the DECODER family (msmp_timing_*), which keeps counting no-grad forwards alone. */
+int msmp_decoder_train_fwd_f32(const float* h, const float* u, int64_t n_nodes, int tw, const float* w1,
+                               const float* b1, const float* w2, const float* b2, float dt, float* out, msmp_stream_t stream);
+int msmp_decoder2d_train_fwd_f32(const float* hd, const float* u, int64_t n_nodes, int tw, const float* w1,
+                                 const float* b1, const float* w2, const float* b2, float dt, float* out, msmp_stream_t stream);
+int msmp_decoder_gated_train_fwd_f32(const float* h, int ld, const float* u, int64_t n_nodes, int width, int tw, const float* gate_w1,
+                                     const float* gate_b1, const float* gate_w2, const float* gate_b2, const float* diff_w1, const float* diff_b1,
+                                     const float* diff_w2, const float* diff_b2, float dt, float* out, msmp_stream_t stream);
+int msmp_decoder2d_gated_train_fwd_f32(const float* hd, int ld, const float* u, int64_t n_nodes, int width, int tw, const float* gate_w1,
+                                       const float* gate_b1, const float* gate_w2, const float* gate_b2, const float* diff_w1, const float* diff_b1,
+                                       const float* diff_w2, const float* diff_b2, float dt, float* out, msmp_stream_t stream);
+
+/* Backward of the decoders: from grad_out (the gradient of `out`, same shape), the forward's inputs and weights to dh (the gradient of the
+ * rows, COMPACT whatever the forward's row stride: [N,128], [N,2,128], [N,164], [N,2,164]) and the gradients of the weights in the layouts of
+ * the weights.  Every element of every output is written, nothing is accumulated; no gradient for u or dt.  Nothing the forward computed is
+ * needed: the Swish pre-activations (gated: both networks' outputs too) are recomputed from the rows.  Plain fp32 fmaf: no range status.
+ * One launch of at most 512 workgroups (16 nodes per pass, grid-stride beyond 8 192 nodes), each writing its sums of the weight gradients to
+ * its own row of `workspace`, then a second small launch that adds the rows in a fixed order: no atomics, no memset, no synchronisation,
+ * capturable, the same bits on every call; a node's dh row depends on that node's row, its grad_out row and the weights only.
+ * workspace: msmp_decoder_bwd_workspace_bytes(comps (1 | 2), gated (0 | 1), width, tw) bytes, independent of n_nodes (512 partial rows);
+ * 0 for a decoder that does not exist.  MSMP_ERR_WORKSPACE if workspace_bytes is below it.
+ * Refusals as the forward entries': null pointers (workspace included) and n_nodes outside 1 .. 2^31 - 1 MSMP_ERR_ARG, any other time
+ * window / width MSMP_ERR_UNSUPPORTED before anything is launched, gated: ld < comps * width MSMP_ERR_ARG.
+ *   msmp_decoder_bwd_f32:  euler != 0: the forward had a u (out = u[:, -1:] + cumsum(dt) diff: d diff = grad_out cumsum(dt));
+ *                          euler == 0: u == NULL there (d diff = grad_out).  tw 20 / 25 / 50.
+ *   msmp_decoder2d_bwd_f32: hd [N,2,128], tw 25 / 50.
+ *   gated (width 164, tw 25): d scale = grad_out (cumsum(dt) diff - u*), d diff = grad_out cumsum(dt) scale, u* = u[:, -1] in 1-D and
+ *                          u[:, co tw + t] in 2-D; dgate_* / ddiff_*: the gradients of the two networks. */
+size_t msmp_decoder_bwd_workspace_bytes(int comps, int gated, int width, int tw);
+int msmp_decoder_bwd_f32(const float* grad_out, const float* h, int64_t n_nodes, int tw, int euler, const float* w1, const float* b1,
+                         const float* w2, const float* b2, float dt, float* dh, float* dw1, float* db1, float* dw2, float* db2,
+                         void* workspace, size_t workspace_bytes, msmp_stream_t stream);
+int msmp_decoder2d_bwd_f32(const float* grad_out, const float* hd, int64_t n_nodes, int tw, const float* w1, const float* b1,
+                           const float* w2, const float* b2, float dt, float* dh, float* dw1, float* db1, float* dw2, float* db2,
+                           void* workspace, size_t workspace_bytes, msmp_stream_t stream);
+int msmp_decoder_gated_bwd_f32(const float* grad_out, const float* h, int ld, const float* u, int64_t n_nodes, int width, int tw,
+                               const float* gate_w1, const float* gate_b1, const float* gate_w2, const float* gate_b2, const float* diff_w1,
+                               const float* diff_b1, const float* diff_w2, const float* diff_b2, float dt, float* dh, float* dgate_w1,
+                               float* dgate_b1, float* dgate_w2, float* dgate_b2, float* ddiff_w1, float* ddiff_b1, float* ddiff_w2,
+                               float* ddiff_b2, void* workspace, size_t workspace_bytes, msmp_stream_t stream);
+int msmp_decoder2d_gated_bwd_f32(const float* grad_out, const float* hd, int ld, const float* u, int64_t n_nodes, int width, int tw,
+                                 const float* gate_w1, const float* gate_b1, const float* gate_w2, const float* gate_b2, const float* diff_w1,
+                                 const float* diff_b1, const float* diff_w2, const float* diff_b2, float dt, float* dh, float* dgate_w1,
+                                 float* dgate_b1, float* dgate_w2, float* dgate_b2, float* ddiff_w1, float* ddiff_b1, float* ddiff_w2,
+                                 float* ddiff_b2, void* workspace, size_t workspace_bytes, msmp_stream_t stream);
 
 /* `double_mlp` of the *2D solver classes, experiments/models_gnn2D.py:66-70 (nn.Linear(128, 256) + Swish; the Unflatten is a view):
  * out [rows, n_out] = Swish(x [rows, k] w^T + bias), w [n_out, k] in nn.Linear's layout; n_out a multiple of 128, k a multiple of 4 up to 288.

@@ -67,6 +67,17 @@ SIGNATURES = {
     'msmp_decoder2d_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
     'msmp_decoder_gated_f32': (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_int] + [c_void_p] * 8 + [c_float, c_void_p, c_void_p]),
     'msmp_decoder2d_gated_f32': (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_int] + [c_void_p] * 8 + [c_float, c_void_p, c_void_p]),
+    'msmp_decoder_train_fwd_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
+    'msmp_decoder2d_train_fwd_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
+    'msmp_decoder_gated_train_fwd_f32': (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_int] + [c_void_p] * 8 + [c_float, c_void_p, c_void_p]),
+    'msmp_decoder2d_gated_train_fwd_f32': (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_int] + [c_void_p] * 8 + [c_float, c_void_p, c_void_p]),
+    'msmp_decoder_bwd_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'msmp_decoder_bwd_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int] + [c_void_p] * 4 + [c_float] + [c_void_p] * 5 + [c_void_p, c_size_t, c_void_p]),
+    'msmp_decoder2d_bwd_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int] + [c_void_p] * 4 + [c_float] + [c_void_p] * 5 + [c_void_p, c_size_t, c_void_p]),
+    'msmp_decoder_gated_bwd_f32': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int] + [c_void_p] * 8 + [c_float] + [c_void_p] * 9
+                                   + [c_void_p, c_size_t, c_void_p]),
+    'msmp_decoder2d_gated_bwd_f32': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int] + [c_void_p] * 8 + [c_float] + [c_void_p] * 9
+                                     + [c_void_p, c_size_t, c_void_p]),
     'msmp_node_tail_f32': (c_int, [c_void_p] * 5 + [c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p]),
     'msmp_lem_encoder_nodes_f32': (c_int, [c_void_p] * 5 + [c_int64, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p]),
     'msmp_lem_saved_floats': (c_int64, [c_int64, c_int]),

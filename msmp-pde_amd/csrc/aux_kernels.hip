@@ -479,6 +479,7 @@ static TuneRow g_tune[] = {
     {"wide_proj", 0, ON_OFF},    // 1: the host layer takes msmp_wide_node_proj_f32 at widths other than 128 (wide_node_proj_kernel.hip)
     {"wide_bwd", 1, ANY_INT},    // != 0: under autograd the host's layer at widths other than 128 takes msmp_wide_layer_bwd_f32 (wide_layer_bwd_kernel.hip); 0: PyTorch ops
     {"wide_dec", 1, ANY_INT},    // != 0: the host ends the GLU classes' forward in msmp_decoder_gated_f32 / msmp_decoder2d_gated_f32 (decoder_kernel.hip)
+    {"dec_bwd", 1, ANY_INT},     // != 0: under autograd the host's decoder takes msmp_*_train_fwd_f32 + msmp_*_bwd_f32 (decoder_bwd_kernel.hip); 0: PyTorch ops
 };
 #undef ANY_INT
 #undef ON_OFF

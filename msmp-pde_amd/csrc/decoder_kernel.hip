@@ -6,34 +6,9 @@
 // with compile-time constants: the compiler keeps them in SGPRs (scalar loads).
 // Both kernels give a node to EIGHT lanes, split by position: a lane that kept a whole row and both intermediate arrays in registers
 // would need 256 VGPRs + 250 AGPRs, one wave per SIMD.
-#include "msmp_common.h"
+#include "decoder_geometry.h"      // DecSplit, the argument blocks (shared with decoder_bwd_kernel.hip)
 
 namespace msmp {
-
-template <int TW, int K1, int S1, int K2, int R = H>                // R: length of the row a network reads (the gated decoders: half a 164-wide row)
-struct DecSplit {
-    static constexpr int L1 = (R - K1) / S1 + 1;
-    static constexpr int PP = (L1 + 7) / 8;                          // intermediate positions per lane
-    static constexpr int XW = (PP - 1) * S1 + K1;                    // row values a lane needs
-    static constexpr int OPL = TW > 32 ? 8 : 4;                      // consecutive outputs per lane (multiple of 4: aligned 16-byte LDS reads)
-    static constexpr int MW = OPL + K2 - 1;                          // intermediate values per channel a lane needs for them
-    static constexpr int MW4 = (MW + 3) / 4;
-    static constexpr int LP = ((7 * OPL + 4 * MW4 > L1 ? 7 * OPL + 4 * MW4 : L1) + 3) / 4 * 4 + 4;      // padded row of the LDS table
-    static constexpr int NODES = 8 * LP * 4 * 32 <= 49152 ? 32 : 16;  // nodes per workgroup (LDS <= 48 KB)
-    static_assert(L1 - K2 + 1 == TW && 8 * OPL >= TW, "decoder geometry");
-};
-
-struct DecArgs {
-    const float* h;      // [N,128]
-    const float* u;      // [N,tw] (nullptr: the decoder output alone, what MSSMP_PDE_Solver_sub returns, models_gnn.py:1679-1682)
-    long n_nodes;
-    const float* w1;     // [8][k1]
-    const float* b1;     // [8]
-    const float* w2;     // [8][k2]
-    const float* b2;     // [1]
-    float dt;
-    float* out;          // [N,tw]
-};
 
 // ----------------------------------------------------------------------------------------------
 // Lane q (0..7) of a node computes the intermediate positions [q PP, (q + 1) PP) of all eight channels from a 26-28-value window of
@@ -133,18 +108,6 @@ __global__ __launch_bounds__(256) void decoder_split_kernel(DecArgs a) {
 // Summation order: an intermediate starts from its bias and adds the taps of input row 0, then of row 1, ascending; an output adds,
 // per channel, its taps ascending from 0, then the eight channel sums as a tree (pairs, pairs of pairs, halves), then the bias.
 // ----------------------------------------------------------------------------------------------
-struct Dec2Args {
-    const float* hd;     // [N, 2, 128]
-    const float* u;      // [N, 2*tw]
-    long n_nodes;
-    const float* w1;     // [8][2][k1]
-    const float* b1;     // [8]
-    const float* w2;     // [2][8][k2]
-    const float* b2;     // [2]
-    float dt;
-    float* out;          // [N, 2*tw]
-};
-
 template <int TW, int K1, int S1, int K2>
 __global__ __launch_bounds__(256) void decoder2d_split_kernel(Dec2Args a) {
     using G = DecSplit<TW, K1, S1, K2>;
@@ -246,23 +209,6 @@ __global__ __launch_bounds__(256) void decoder2d_split_kernel(Dec2Args a) {
 // taps of input component 0, then of component 1, ascending; an output adds, per intermediate channel, its taps ascending from 0, then the
 // eight channel sums as a tree (pairs, pairs of pairs, halves), then the bias; cumsum(dt) is formed by repeated float32 addition.
 // ----------------------------------------------------------------------------------------------
-struct DecNet {
-    const float* w1;     // [8][C][6]
-    const float* b1;     // [8]
-    const float* w2;     // [C][8][15]
-    const float* b2;     // [C]
-};
-
-struct DecGatedArgs {
-    const float* h;      // 1-D: [N, ld] rows of 164;  2-D: [N, ld] rows of 2 x 164 (hd)
-    long ld;             // row stride in floats
-    const float* u;      // [N, C tw]
-    long n_nodes;
-    DecNet gate, diff;
-    float dt;
-    float* out;          // [N, C tw]
-};
-
 // One network of lane q: o[co][i] = output t0 + i of component co.  row: the node's (clamped) row, already offset to the network's half;
 // component ci starts ci * CS floats further.  Ends with a barrier: the table may be written again.
 template <class G, int C, int CS, int R, int K1, int S1, int K2>
@@ -412,50 +358,73 @@ __global__ __launch_bounds__(256) void decoder2d_gated_kernel(DecGatedArgs a) {
 
 using namespace msmp;
 
+// One launcher per kernel.  `timed`: the inference entries, inside the event bracket of the DECODER family; the forward-for-training
+// entries (msmp_*_train_fwd_f32: the forward half of the decoder under autograd, whose backward is decoder_bwd_kernel.hip) launch the SAME
+// kernels outside it, so the family keeps counting the launches of no-grad forwards only.
 #define MSMP_DEC_SPLIT(KERNEL, TW_, K1_, S1_, K2_) do { using G_ = DecSplit<TW_, K1_, S1_, K2_>; \
         hipLaunchKernelGGL((KERNEL<TW_, K1_, S1_, K2_>), dim3((unsigned)((n_nodes + G_::NODES - 1) / G_::NODES)), dim3(G_::NODES * 8), 0, st, a); } while (0)
 
-extern "C" int msmp_decoder2d_f32(const float* hd, const float* u, int64_t n_nodes, int tw, const float* w1, const float* b1,
-                                  const float* w2, const float* b2, float dt, float* out, msmp_stream_t stream) {
-    MSMP_REQUIRE(hd && u && w1 && b1 && w2 && b2 && out, MSMP_ERR_ARG, "msmp_decoder2d_f32: null pointer");
-    MSMP_REQUIRE(n_nodes > 0 && n_nodes < (1L << 31), MSMP_ERR_ARG, "msmp_decoder2d_f32: bad n_nodes");
+static int decoder2d(const char* who, bool timed, const float* hd, const float* u, int64_t n_nodes, int tw, const float* w1, const float* b1,
+                     const float* w2, const float* b2, float dt, float* out, msmp_stream_t stream) {
+    MSMP_REQUIRE(hd && u && w1 && b1 && w2 && b2 && out, MSMP_ERR_ARG, "%s: null pointer", who);
+    MSMP_REQUIRE(n_nodes > 0 && n_nodes < (1L << 31), MSMP_ERR_ARG, "%s: bad n_nodes", who);
     Dec2Args a{hd, u, (long)n_nodes, w1, b1, w2, b2, dt, out};
     hipStream_t st = (hipStream_t)stream;
-    timing_begin(MSMP_K_DECODER, st);
+    if (timed) timing_begin(MSMP_K_DECODER, st);
     switch (tw) {   // experiments/models_gnn2D.py:79-88
         case 25: MSMP_DEC_SPLIT(decoder2d_split_kernel, 25, 16, 3, 14); break;
         case 50: MSMP_DEC_SPLIT(decoder2d_split_kernel, 50, 12, 2, 10); break;
         default:
-            set_error("msmp_decoder2d_f32: time_window %d (the reference defines 25, 50)", tw);
+            set_error("%s: time_window %d (the reference defines 25, 50)", who, tw);
             return MSMP_ERR_UNSUPPORTED;
     }
-    timing_end(MSMP_K_DECODER, st);
+    if (timed) timing_end(MSMP_K_DECODER, st);
     return check_launch("decoder2d_split_kernel");
 }
 
-extern "C" int msmp_decoder_f32(const float* h, const float* u, int64_t n_nodes, int tw, const float* w1, const float* b1,
-                                const float* w2, const float* b2, float dt, float* out, msmp_stream_t stream) {
-    MSMP_REQUIRE(h && w1 && b1 && w2 && b2 && out, MSMP_ERR_ARG, "msmp_decoder_f32: null pointer");
-    MSMP_REQUIRE(n_nodes > 0 && n_nodes < (1L << 31), MSMP_ERR_ARG, "msmp_decoder_f32: bad n_nodes");
+static int decoder1d(const char* who, bool timed, const float* h, const float* u, int64_t n_nodes, int tw, const float* w1, const float* b1,
+                     const float* w2, const float* b2, float dt, float* out, msmp_stream_t stream) {
+    MSMP_REQUIRE(h && w1 && b1 && w2 && b2 && out, MSMP_ERR_ARG, "%s: null pointer", who);
+    MSMP_REQUIRE(n_nodes > 0 && n_nodes < (1L << 31), MSMP_ERR_ARG, "%s: bad n_nodes", who);
     DecArgs a{h, u, (long)n_nodes, w1, b1, w2, b2, dt, out};
     hipStream_t st = (hipStream_t)stream;
-    timing_begin(MSMP_K_DECODER, st);
+    if (timed) timing_begin(MSMP_K_DECODER, st);
     switch (tw) {   // experiments/models_gnn.py:210-224
         case 20: MSMP_DEC_SPLIT(decoder_split_kernel, 20, 15, 4, 10); break;
         case 25: MSMP_DEC_SPLIT(decoder_split_kernel, 25, 16, 3, 14); break;
         case 50: MSMP_DEC_SPLIT(decoder_split_kernel, 50, 12, 2, 10); break;
         default:
-            set_error("msmp_decoder_f32: time_window %d (the reference defines 20, 25, 50)", tw);
+            set_error("%s: time_window %d (the reference defines 20, 25, 50)", who, tw);
             return MSMP_ERR_UNSUPPORTED;
     }
-    timing_end(MSMP_K_DECODER, st);
+    if (timed) timing_end(MSMP_K_DECODER, st);
     return check_launch("decoder_split_kernel");
 }
 #undef MSMP_DEC_SPLIT
 
+extern "C" int msmp_decoder2d_f32(const float* hd, const float* u, int64_t n_nodes, int tw, const float* w1, const float* b1,
+                                  const float* w2, const float* b2, float dt, float* out, msmp_stream_t stream) {
+    return decoder2d("msmp_decoder2d_f32", true, hd, u, n_nodes, tw, w1, b1, w2, b2, dt, out, stream);
+}
+
+extern "C" int msmp_decoder2d_train_fwd_f32(const float* hd, const float* u, int64_t n_nodes, int tw, const float* w1, const float* b1,
+                                            const float* w2, const float* b2, float dt, float* out, msmp_stream_t stream) {
+    return decoder2d("msmp_decoder2d_train_fwd_f32", false, hd, u, n_nodes, tw, w1, b1, w2, b2, dt, out, stream);
+}
+
+extern "C" int msmp_decoder_f32(const float* h, const float* u, int64_t n_nodes, int tw, const float* w1, const float* b1,
+                                const float* w2, const float* b2, float dt, float* out, msmp_stream_t stream) {
+    return decoder1d("msmp_decoder_f32", true, h, u, n_nodes, tw, w1, b1, w2, b2, dt, out, stream);
+}
+
+extern "C" int msmp_decoder_train_fwd_f32(const float* h, const float* u, int64_t n_nodes, int tw, const float* w1, const float* b1,
+                                          const float* w2, const float* b2, float dt, float* out, msmp_stream_t stream) {
+    return decoder1d("msmp_decoder_train_fwd_f32", false, h, u, n_nodes, tw, w1, b1, w2, b2, dt, out, stream);
+}
+
 // The gated decoders exist for the one geometry the reference defines (hidden width 164, time_window 25): anything else is refused by
 // value before a launch, and the host keeps its PyTorch ops.  msmp_tune("wide_dec", ...) is read by the host only.
-static int decoder_gated(const char* who, bool two_d, const float* h, int ld, const float* u, int64_t n_nodes, int width, int tw,
+static int decoder_gated(const char* who, bool two_d, bool timed, const float* h, int ld, const float* u, int64_t n_nodes, int width, int tw,
                          const DecNet& gate, const DecNet& diff, float dt, float* out, msmp_stream_t stream) {
     MSMP_REQUIRE(h && u && out && gate.w1 && gate.b1 && gate.w2 && gate.b2 && diff.w1 && diff.b1 && diff.w2 && diff.b2, MSMP_ERR_ARG,
                  "%s: null pointer", who);
@@ -467,23 +436,23 @@ static int decoder_gated(const char* who, bool two_d, const float* h, int ld, co
     using G = DecSplit<25, 6, 2, 15, 82>;
     const dim3 grid((unsigned)((n_nodes + G::NODES - 1) / G::NODES)), block(G::NODES * 8);
     hipStream_t st = (hipStream_t)stream;
-    timing_begin(MSMP_K_DECODER, st);
+    if (timed) timing_begin(MSMP_K_DECODER, st);
     if (two_d) hipLaunchKernelGGL((decoder2d_gated_kernel<164, 25, 6, 2, 15>), grid, block, 0, st, a);      // models_gnn2D.py:1291-1298
     else hipLaunchKernelGGL((decoder_gated_kernel<164, 25, 6, 2, 15>), grid, block, 0, st, a);              // models_gnn.py:1455-1456
-    timing_end(MSMP_K_DECODER, st);
+    if (timed) timing_end(MSMP_K_DECODER, st);
     return check_launch(two_d ? "decoder2d_gated_kernel" : "decoder_gated_kernel");
 }
 
-extern "C" int msmp_decoder_gated_f32(const float* h, int ld, const float* u, int64_t n_nodes, int width, int tw, const float* gate_w1,
-                                      const float* gate_b1, const float* gate_w2, const float* gate_b2, const float* diff_w1, const float* diff_b1,
-                                      const float* diff_w2, const float* diff_b2, float dt, float* out, msmp_stream_t stream) {
-    return decoder_gated("msmp_decoder_gated_f32", false, h, ld, u, n_nodes, width, tw, DecNet{gate_w1, gate_b1, gate_w2, gate_b2},
-                         DecNet{diff_w1, diff_b1, diff_w2, diff_b2}, dt, out, stream);
-}
+#define MSMP_DEC_GATED_ENTRY(NAME, TWO_D, TIMED)                                                                                              \
+    extern "C" int NAME(const float* h, int ld, const float* u, int64_t n_nodes, int width, int tw, const float* gate_w1, const float* gate_b1, \
+                        const float* gate_w2, const float* gate_b2, const float* diff_w1, const float* diff_b1, const float* diff_w2,           \
+                        const float* diff_b2, float dt, float* out, msmp_stream_t stream) {                                                     \
+        return decoder_gated(#NAME, TWO_D, TIMED, h, ld, u, n_nodes, width, tw, DecNet{gate_w1, gate_b1, gate_w2, gate_b2},                     \
+                             DecNet{diff_w1, diff_b1, diff_w2, diff_b2}, dt, out, stream);                                                      \
+    }
+MSMP_DEC_GATED_ENTRY(msmp_decoder_gated_f32, false, true)
+MSMP_DEC_GATED_ENTRY(msmp_decoder2d_gated_f32, true, true)
+MSMP_DEC_GATED_ENTRY(msmp_decoder_gated_train_fwd_f32, false, false)
+MSMP_DEC_GATED_ENTRY(msmp_decoder2d_gated_train_fwd_f32, true, false)
+#undef MSMP_DEC_GATED_ENTRY
 
-extern "C" int msmp_decoder2d_gated_f32(const float* hd, int ld, const float* u, int64_t n_nodes, int width, int tw, const float* gate_w1,
-                                        const float* gate_b1, const float* gate_w2, const float* gate_b2, const float* diff_w1, const float* diff_b1,
-                                        const float* diff_w2, const float* diff_b2, float dt, float* out, msmp_stream_t stream) {
-    return decoder_gated("msmp_decoder2d_gated_f32", true, hd, ld, u, n_nodes, width, tw, DecNet{gate_w1, gate_b1, gate_w2, gate_b2},
-                         DecNet{diff_w1, diff_b1, diff_w2, diff_b2}, dt, out, stream);
-}

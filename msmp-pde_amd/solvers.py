@@ -12,8 +12,8 @@ Reference classes:
 Inference (no autograd) runs on HIP kernels end to end: the encoder (msmp_lem_encoder_nodes_f32 with lemoutput_mlp fused, or
 msmp_mlp2_swish_f32 for embedding_mlp), the L x [message -> mean -> update -> InstanceNorm (-> gate blend)] loop
 (msmp_mp_layer_f32), `double_mlp` of the 2-D classes (msmp_linear_swish_f32) and the decoder CNN with the Euler update
-(msmp_decoder_f32 / msmp_decoder2d_f32).  Under autograd the layers and the LEM encoder use their
-HIP forward / backward pairs (autograd.py, lem.py) and the small encoder / decoder modules PyTorch-ROCm ops.  `pde.L`,
+(msmp_decoder_f32 / msmp_decoder2d_f32).  Under autograd the layers, the LEM encoder and the decoder CNN use their
+HIP forward / backward pairs (autograd.py, lem.py, decoder.py) and the small encoder modules PyTorch-ROCm ops.  `pde.L`,
 `pde.tmax`, `pde.dt` are read at call time (they are mutated after construction, experiments/train.py:355-358).  Compute
 dtype is float32; the result is returned in the dtype of `data.x`.
 """
@@ -28,7 +28,7 @@ from .graph import structure_of
 from .layers import GNN_Layer, GNN_LayerLin, Swish, mp_layer
 from .lem import LEM, LEMS
 from .reductions import bias_add
-from . import wide
+from . import decoder, wide
 from .wide import _wide_fused, lemoutput_mlp
 
 _DECODER = {20: (15, 4, 10), 25: (16, 3, 14), 50: (12, 2, 10)}   # models_gnn.py:210-224; models_gnn2D.py:79-88
@@ -523,8 +523,25 @@ class _SolverBase(nn.Module):
 
         return self._decode(h, u, u_in, dt, tw)
 
+    def _decode_train(self, kind, h, u, tw, fused, *nets):
+        """The decoder under autograd on the HIP kernels (decoder.DecoderFunction: the forward kernel + one backward call), or None where
+        the PyTorch ops apply: switch "dec_bwd" 0 (`fused`: the test of the switches), tensors the kernels do not read, a `u` that
+        requires grad, and sizes the entries refuse by value (remembered: not asked again)."""
+        ok = lambda t: t.is_cuda and t.dtype == torch.float32
+        if not (ok(h) and ok(u) and not u.requires_grad) or getattr(self, '_dec_bwd_refused', None) == (h.shape[1], tw) or not fused():
+            return None
+        rows = self.double_mlp(h) if self.TWO_D else h
+        out = decoder.decode(kind, rows, None if self.RETURN_DIFF else u, tw, self.pde.dt, *nets)
+        if out is None:
+            self._dec_bwd_refused = (h.shape[1], tw)
+        return out
+
     def _decode(self, h, u, u_in, dt, tw):
         grad_path = torch.is_grad_enabled() and (h.requires_grad or any(p.requires_grad for p in self.output_mlp.parameters()))
+        if grad_path:
+            out = self._decode_train('2d' if self.TWO_D else '1d', h, u, tw, lambda: lib().msmp_tune_query(b'dec_bwd'), self.output_mlp)
+            if out is not None:
+                return out.to(u_in.dtype)
         if self.TWO_D and grad_path:    # models_gnn2D.py:125-141
             diff = _decoder_autograd(self.double_mlp(h), self.output_mlp[0], self.output_mlp[2])
             out = (u.view(-1, 2, tw) + dt.view(1, 1, tw) * diff).flatten(1, 2)
@@ -678,8 +695,9 @@ class _GLUBase(_SolverBase):
     models_gnn2D.py:1198-1366; no sigmoid on `scale`, as in the reference).  Layers: the width-generic HIP path
     (wide._mp_layer_wide); without grad the LEM recurrence is one HIP launch (msmp_lem_encoder_wide_f32), lemoutput_mlp two HIP row
     GEMMs, double_mlp one (msmp_linear_f32) and the two small CNNs with the gated update one launch (msmp_decoder_gated_f32 /
-    msmp_decoder2d_gated_f32; switch "wide_dec").  Under autograd, with that switch or the fused width-generic path off, and at a width or
-    time window the entry refuses, the decoder is PyTorch-ROCm ops."""
+    msmp_decoder2d_gated_f32; switch "wide_dec").  Under autograd the decoder is the same kernel + one backward call
+    (decoder.DecoderFunction; switch "dec_bwd").  With the switches or the fused width-generic path off, and at a width or time window the
+    entries refuse, the decoder is PyTorch-ROCm ops."""
     GATED, LEM_ENCODER, LAYER = True, True, GNN_LayerLin
 
     def __init__(self, pde, time_window=25, hidden_features=164, hidden_layer=6, eq_variables={}, save_state=None):
@@ -712,6 +730,10 @@ class _GLUBase(_SolverBase):
 
     def _decode(self, h, u, u_in, dt, tw):
         out = self._decode_hip(h, u, tw)
+        mods = (self.output_mlp_gate, self.output_mlp_diff) + ((self.double_mlp,) if self.TWO_D else ())
+        if out is None and torch.is_grad_enabled() and (h.requires_grad or any(p.requires_grad for m in mods for p in m.parameters())):
+            out = self._decode_train('gated2d' if self.TWO_D else 'gated', h, u, tw, lambda: _wide_fused(b'dec_bwd'),
+                                     self.output_mlp_gate, self.output_mlp_diff)
         if out is not None:
             return out.to(u_in.dtype)
         half = h.shape[1] // 2
