@@ -52,11 +52,12 @@ extern "C" {
 
 typedef void* msmp_stream_t;
 
-/* ABI version: 410 = msmp_mp_layer_decode_f32 and msmp_decoder_t removed;
+/* ABI version: 420 = the five entries of the 128-wide LEM training pair removed (msmp_lem_train_fwd_wide_f32 / _bwd_wide_f32 serve every
+ * width) and the blob of msmp_pack_lem_f32 without its last section, which only that pair read; 410 = msmp_mp_layer_decode_f32 and msmp_decoder_t removed;
  * 400 = round 4 (msmp_tiles_t: listed, period_tiles, period_nodes; msmp_build_tiles writes 3 statistics);
  * 300 = round 3 (msmp_last_status, msmp_tiles_t checked on every entry point that takes one).  Bumped whenever a
  * prototype or a blob layout changes; the ctypes host refuses a library whose version is not the one it was written for. */
-#define MSMP_ABI_VERSION 410
+#define MSMP_ABI_VERSION 420
 int msmp_version(void);
 const char* msmp_last_error(void);
 
@@ -94,7 +95,7 @@ int msmp_last_status(int* flags_out, int reset);
  *             workgroups only (same bits either way).
  *   "lem_wide" 1 (default): the host's no-grad LEM at widths other than 128 is one msmp_lem_encoder_wide_f32 launch; 0: the loop of two
  *             library GEMMs + msmp_wide_lem_z_f32 / _y_f32 per time step (the entry itself does not read the key).
- *   "lem_wide_train" 1 (default): under autograd the host's LEM at widths other than 128 is msmp_lem_train_fwd_wide_f32 + msmp_lem_train_bwd_wide_f32 +
+ *   "lem_wide_train" 1 (default): under autograd the host's LEM at every width is msmp_lem_train_fwd_wide_f32 + msmp_lem_train_bwd_wide_f32 +
  *             one msmp_grad_weights_cat_f32; 0: the PyTorch ops of the restated cell, differentiated by autograd (the entries themselves do
  *             not read the key; any value other than 0 selects the kernels).
  *   "wide_msg" 1 (default): the host's no-grad layer at widths other than 128 evaluates the message half of a head as one
@@ -459,33 +460,6 @@ int msmp_lem_encoder_nodes_f32(const float* u, const float* pos_x, const float* 
                                float* h_out, msmp_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
- * LEM encoder, training pair (replaces lem_cuda.forward / lem_cuda.backward as LEMFunction
- * uses them, experiments/models_gnn.py:285-302)
- * ------------------------------------------------------------------------------------------- */
-/* LEMFunction.forward (:287-295): the recurrence of msmp_lem_encoder_f32 (no lemoutput_mlp, exact-fp32 MFMA) that also
- * saves what the backward needs, as the reference saves all_X / all_X2 / all_multi_scales / all_lin_new_z_state:
- * saved [6][N][T][128] floats (msmp_lem_saved_floats) = dt*sigmoid(g2), tanh(g3), dt*sigmoid(g1), tanh(lin), y_{t-1} (the state
- * entering step t; y0 at t = 0), z_t.
- * xin / packed as for msmp_lem_encoder_f32; y_out [N,128] = all_y[-1]. */
-int64_t msmp_lem_saved_floats(int64_t n_nodes, int t_len);
-/* y0 / z0 [N,128]: the initial states (LEMcuda.forward's `states`, :325-332; both NULL = zeros); z_out [N,128] = all_z[-1] (or
- * NULL); saved may be NULL when no backward follows (the state-carrying LEMS of the `Save` variants under no_grad, :345-362). */
-int msmp_lem_train_fwd_f32(const float* xin, int64_t n_nodes, int t_len, int ninp, float dt, const float* packed,
-                           const float* y0, const float* z0, float* saved, float* y_out, float* z_out, msmp_stream_t stream);
-/* The transposed recurrent blocks of weights / weights_lin_z for the backward kernel (16 chunks of [128][32]). */
-int64_t msmp_packed_lem_bwd_floats(void);
-int msmp_pack_lem_bwd_f32(const float* weights, const float* weights_lin_z, int ninp, float* packed_out,
-                          msmp_stream_t stream);
-/* LEMFunction.backward (:296-302), the back-propagation through time: grad_y [N,128] = dL/d all_y[-1] ->
- * dg_out [N][T][512] = dL/d(pre-activations) per node and step, columns (g1 | g2 | g3 | lin) in the row order of
- * `weights` then `weights_lin_z`.  The parameter gradients are GEMMs of it over the N*T rows:
- *   d weights = dg[:, :384]^T [y_{t-1} | x_t],  d weights_lin_z = dg[:, 384:]^T [z_t | x_t],  d bias* = column sums
- * (y, z = planes 4, 5 of `saved`; y_{-1} = y0, the forward's initial state, or 0).  Like the reference's use of it, no gradient
- * of the step inputs is produced (:300-302), nor of the initial states (they are carried constants, :350-353). */
-int msmp_lem_train_bwd_f32(const float* grad_y, const float* saved, const float* y0, const float* z0, int64_t n_nodes, int t_len,
-                           float dt, const float* packed_bwd, float* dg_out, msmp_stream_t stream);
-
-/* ---------------------------------------------------------------------------------------------
  * Training backward of a message-passing layer: the non-GEMM pieces.  The host layer
  * re-evaluates the layer in materialised form with library GEMMs (the reference does the same through autograd over
  * experiments/models_gnn.py:61-149) and calls these between them.
@@ -613,9 +587,13 @@ int msmp_pack_lem_wide_f32(const float* weights, const float* weights_lin_z, con
  * required pointer; n_nodes = 0 is a no-op.  A step input with |x| > 255 or not finite raises MSMP_STATUS_INPUT_RANGE. */
 int msmp_lem_encoder_wide_f32(const float* xin, int64_t n_nodes, int t_len, int ninp, int width, float dt, const float* packed,
                               const float* y0, const float* z0, float* y_out, float* z_out, msmp_stream_t stream);
-/* The TRAINING pair of that cell at any hidden width 1 <= width <= 256 (lem_wide_train_kernel.hip): msmp_lem_train_fwd_f32 / _bwd_f32 with the
- * width as an argument, Wp = 32 ceil(width / 32), ldg = 128 ceil(width / 128).  Three-way bf16 split products (fp32-exact, as the 128-wide
- * pair): no input range, the range status is neither read nor raised.  Blobs: weights [3 width, width + ninp], weights_lin_z
+/* The TRAINING pair of that cell at any hidden width 1 <= width <= 256, 128 included (lem_wide_train_kernel.hip): it
+ * replaces lem_cuda.forward / lem_cuda.backward as LEMFunction uses them (experiments/models_gnn.py:285-302).  The forward is the recurrence
+ * (no lemoutput_mlp) that also saves what the backward needs, as the reference saves all_X / all_X2 / all_multi_scales /
+ * all_lin_new_z_state; the backward is the back-propagation through time down to dL/d(pre-activations), of which the parameter gradients
+ * are GEMMs over the N*T rows:  d weights = dg[g1 | g2 | g3]^T [y_{t-1} | x_t],  d weights_lin_z = dg[lin]^T [z_t | x_t],  d bias* = column
+ * sums.  Wp = 32 ceil(width / 32), ldg = 128 ceil(width / 128).  Three-way bf16 split products (fp32-exact): no input range, the range
+ * status is neither read nor raised.  Blobs: weights [3 width, width + ninp], weights_lin_z
  * [width, width + ninp], bias [3 width], bias_lin_z [width], ninp 1..8;
  *   msmp_packed_lem_wide_train_floats = 6144 kt^2 + 1152 kt, msmp_packed_lem_wide_bwd_floats = 6144 kt^2 floats (kt = ceil(width / 32)),
  * 0 (and msmp_last_error) for a width or ninp outside the range.  All blobs, `saved` and `dg_out` are 16-byte aligned. */
@@ -636,8 +614,8 @@ int msmp_lem_train_fwd_wide_f32(const float* xin, int64_t n_nodes, int t_len, in
                                 const float* y0, const float* z0, float* saved, float* y_out, float* z_out, msmp_stream_t stream);
 /* grad_y [n_nodes, width] = dL/dy_T -> dg_out: per node and step the gates (g1 | g2 | g3 | lin), ldg columns each, columns width .. ldg - 1
  * written as 0, so every gate is one or two 128-column A operands (row stride 4 ldg) of msmp_grad_weights_cat_f32 with B = [plane 4 (lin:
- * plane 5) of saved, row stride Wp | x_t].  y0 / z0: the forward's initial states (both or none).  Also MSMP_ERR_ARG for dt = 0.  No
- * gradient of the step inputs or of the initial states, as at 128. */
+ * plane 5) of saved, row stride Wp | x_t].  y0 / z0: the forward's initial states (both or none).  Also MSMP_ERR_ARG for dt = 0.  Like the
+ * reference's use of it, no gradient of the step inputs is produced (:300-302), nor of the initial states (carried constants, :350-353). */
 int msmp_lem_train_bwd_wide_f32(const float* grad_y, const float* saved, const float* y0, const float* z0, int64_t n_nodes, int t_len,
                                 int width, float dt, const float* packed_bwd, float* dg_out, msmp_stream_t stream);
 /* The message half of one head at any hidden width 1 <= width <= 256 in ONE launch, nothing edge-sized in memory

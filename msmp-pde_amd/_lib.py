@@ -24,7 +24,7 @@ MSMP_LAYER_LIN = 1
 MSMP_ERR_UNSUPPORTED = -2
 MSMP_MAX_VARS = 8
 HIDDEN = 128
-MSMP_ABI_VERSION = 410          # include/msmp_pde.h: the library must report exactly this
+MSMP_ABI_VERSION = 420          # include/msmp_pde.h: the library must report exactly this
 MSMP_STATUS_INPUT_RANGE, MSMP_STATUS_NODE_SATURATED, MSMP_STATUS_NONFINITE = 1, 2, 4
 
 # name -> (restype, argtypes); must list every symbol include/msmp_pde.h declares
@@ -80,11 +80,6 @@ SIGNATURES = {
                                      + [c_void_p, c_size_t, c_void_p]),
     'msmp_node_tail_f32': (c_int, [c_void_p] * 5 + [c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p]),
     'msmp_lem_encoder_nodes_f32': (c_int, [c_void_p] * 5 + [c_int64, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p]),
-    'msmp_lem_saved_floats': (c_int64, [c_int64, c_int]),
-    'msmp_lem_train_fwd_f32': (c_int, [c_void_p, c_int64, c_int, c_int, c_float] + [c_void_p] * 7),
-    'msmp_packed_lem_bwd_floats': (c_int64, []),
-    'msmp_pack_lem_bwd_f32': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    'msmp_lem_train_bwd_f32': (c_int, [c_void_p] * 4 + [c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     'msmp_edge_concat_f32': (c_int, [c_void_p] * 6 + [c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
     'msmp_mean_bwd_dswish_f32': (c_int, [c_void_p] * 4 + [c_int64, c_void_p, c_void_p]),
     'msmp_instance_norm_bwd_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p]),

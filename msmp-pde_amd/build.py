@@ -21,7 +21,6 @@ SOURCES = {  # file -> extra flags
     # wave's MFMAs costs more cycles than the two instructions it replaces: 2 480 vs 1 960 cycles per vector half, scripts/prof_lem.py;
     # the SLP vectoriser would re-pack the scalar ops)
     'lem_kernel.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form', '-fno-slp-vectorize'],
-    'lem_train_kernel.hip': [],
     'lem_wide_kernel.hip': [],
     'lem_wide_train_kernel.hip': [],
     'wide_message_kernel.hip': [],

@@ -473,7 +473,7 @@ static TuneRow g_tune[] = {
     {"lem_share", 1, 1, 16, false},  // k LEM launches share the GPU (sub-batches on k streams): a launch plans for CUs / k
     {"lem_tail", 1, ON_OFF},     // 0: every workgroup of the ws3 LEM kernel takes three tiles (no round of one-tile workgroups)
     {"lem_wide", 1, ON_OFF},     // 0: the host keeps the per-step GEMM + pointwise loop at widths other than 128
-    {"lem_wide_train", 1, ANY_INT},  // != 0: under autograd the host's LEM at widths other than 128 takes the training pair of lem_wide_train_kernel.hip; 0: PyTorch ops
+    {"lem_wide_train", 1, ANY_INT},  // != 0: under autograd the host's LEM (every width) takes the training pair of lem_wide_train_kernel.hip; 0: PyTorch ops
     {"wide_msg", 1, ON_OFF},    // 0: the host layer keeps gather + row GEMM + scatter at widths other than 128
     {"wide_tail", 0, ON_OFF},    // 1: the host layer takes msmp_wide_node_tail_f32 at widths other than 128 (wide_node_tail_kernel.hip)
     {"wide_proj", 0, ON_OFF},    // 1: the host layer takes msmp_wide_node_proj_f32 at widths other than 128 (wide_node_proj_kernel.hip)

@@ -1,16 +1,35 @@
-// LEM encoder for TRAINING at ANY hidden width 1 <= W <= 256 (the GLU classes: 164): the width-generic counterparts of lem_train_fwd_kernel
-// and lem_bptt_kernel (lem_train_kernel.hip; its header comment states the cell, the backward recurrences and the saved set).
+// LEM encoder for TRAINING at any hidden width 1 <= W <= 256 (the 128-wide classes and the GLU classes' 164 alike):
+// the T-step recurrence with its per-step activations saved, and its backward pass (back-propagation through time) as one kernel each,
+// replacing `lem_cuda.forward` / `lem_cuda.backward` of the reference's absent extension (experiments/models_gnn.py:285-302:
+// LEMFunction.forward saves all_X, all_X2, all_multi_scales, all_lin_new_z_state ...; LEMFunction.backward returns the gradients of weights,
+// weights_lin_z, bias, bias_lin_z and drops the gradient of `inputs`, :296-302).
 //   msmp_lem_train_fwd_wide_f32   the T-step recurrence from (y0, z0) to (y_T, z_T), saving per step a2, c, a1, d, y_{t-1}, z'
 //   msmp_lem_train_bwd_wide_f32   back-propagation through time: dL/dy_T -> dG = (dg1 | dg2 | dg3 | dl) per node and step
-// The weight gradients are then msmp_grad_weights_cat_f32 jobs over the N*T rows (128 columns of dG each), issued by the host layer.
 //
-// Workgroup shape (the 128-wide one with the 4 waves replaced by KT = ceil(W / 32)): one 32-node tile per workgroup, 64 KT threads; wave ct owns
-// channel tile ct (32 of the Wp = 32 KT channels) of every carried tensor, in accumulator layout, for all T steps.  The B operand of a GEMM
-// (y, z' forward; dg1, dl, dg2, dg3 backward) is PUBLISHED in LDS as bf16 hi / mid / lo fragments in acc order (6 KB per k-tile, 6 KT KB per
-// tensor; ONE area, reused between barriers as in lem_bptt_kernel), and every wave multiplies its own 32 rows of the weight block -- bf16x3
-// A fragments streamed from the L2-resident blob through buffer loads, one k-tile (6 KB per wave) ahead -- with all published fragments: six
-// v_mfma_f32_32x32x16_bf16 per K = 16 step, fp32-exact products (mfma_tiles.h).  No fp16 anywhere, so there is no input range and the
-// kernels neither read nor raise the range status.  Barriers per step: 4 forward, 8 backward.
+// Forward (per step, per node; same cell as lem_kernel.hip):
+//     g = W [y ; x_t] + b;  a1 = dt s(g1);  a2 = dt s(g2);  c = tanh(g3);  z' = (1-a2) z + a2 c
+//     l = Wz [z' ; x_t] + bz;  d = tanh(l);  y' = (1-a1) y + a1 d
+// Backward (t = T-1 .. 0, carrying dy = dL/dy_t and dz = dL/dz_t):
+//     da1 = dy (d - y);  dd = dy a1;  dy <- dy (1-a1);  dl = dd (1-d^2);  dg1 = da1 a1 (1 - a1/dt)
+//     dz += Wz[:, :W]^T dl;  da2 = dz (c - z);  dc = dz a2;  dz <- dz (1-a2);  dg2 = da2 a2 (1 - a2/dt);  dg3 = dc (1-c^2)
+//     dy += W[:, :W]^T (dg1, dg2, dg3)
+// The parameter gradients are then plain GEMMs over the N*T rows (dW = dG[:, :3]^T [y_prev ; x], dWz = dl^T [z' ; x]) and column sums:
+// msmp_grad_weights_cat_f32 jobs of 128 columns of dG each, issued by the host layer.  The saved planes are node-major, so each is directly
+// the row matrix of those GEMMs.
+//
+// Workgroup shape: one 32-node tile per workgroup, 64 KT threads, KT = ceil(W / 32); wave ct owns channel tile ct (32 of the Wp = 32 KT
+// channels) of every carried tensor, in accumulator layout (one node per lane), for all T steps.  A GEMM needs all Wp channels of its B
+// operand (y, z' forward; dg1, dl, dg2, dg3 backward): the operand tensor is PUBLISHED in LDS as bf16 hi / mid / lo MFMA fragments in "acc
+// order" (K step s of k-tile kt of a lane is registers 8 s .. 8 s + 7 of wave kt's accumulator tile, so a publish is a register split + three
+// 16-byte stores, no transposition; 6 KB per k-tile, 6 KT KB per tensor; ONE area, reused between barriers), and every wave multiplies its own
+// 32 rows of the weight block -- bf16x3 A fragments streamed from the L2-resident blob through buffer loads, one k-tile (6 KB per wave) ahead,
+// nothing staged: a wave needs only ITS 32 rows -- with all published fragments: six v_mfma_f32_32x32x16_bf16 per K = 16 step, fp32-exact
+// products (mfma_tiles.h).  No fp16 anywhere, so there is no input range and the kernels neither read nor raise the range status.  Barriers
+// per step: 4 forward, 8 backward.  (The first edition, 128 wide only: v_mfma_f32_32x32x2_f32 with every 16-KB weight chunk staged through
+// LDS, 19 barriers and 256 KB of staging per time step; this shape cut the matrix time per node 2.7x.)
+// Node tiles per workgroup: two (64 nodes, 228 / 247 registers at width 128, two workgroups per CU) halve the weight-fragment traffic but
+// measured the same as one (three workgroups per CU): 30.3 vs 30.0 ms per batch-512 training iteration.  At width 128 the backward holds 180
+// registers (two workgroups per CU) and takes the time of a 163-register edition with three (profiles/r19a_one_lem_training_pair.md).
 // Channels W .. Wp - 1 carry zero weights, zero bias and zero state: their z and y stay exact zeros, their dG is an exact zero, and they are
 // never written to y_out / z_out.  A node's arithmetic depends on nothing but its own row.
 //
@@ -164,8 +183,9 @@ struct LwtFrag {
     u32x4 f[2][3];       // [s][plane] of this wave's 32 rows of one k-tile
 };
 // k-tile i of this wave's stream (4 KT per time step) through BUFFER loads: the descriptor holds the wave's stream base (scalar), the
-// fragment is a scalar offset and the lane one 32-bit vector offset (with global loads the compiler forms, hoists and spills a 64-bit
-// address per fragment: lem_train_kernel.hip)
+// fragment is a scalar offset and the lane one 32-bit vector offset.  With global loads the compiler forms a per-lane 64-bit address for each
+// of the 96 fragments of a time step, hoists them out of the t loop as invariants and spills them (49 scratch stores at the head of the
+// first edition).
 __device__ __forceinline__ void lwt_frag_load(LwtFrag& w, __amdgpu_buffer_rsrc_t stream, int i, unsigned loff) {
 #pragma unroll
     for (int s = 0; s < 2; ++s)
@@ -219,9 +239,10 @@ struct LemWideTrainArgs {
     float *y_out, *z_out;   // [N, W]; z_out may be NULL
 };
 
-// acc (tile ct) = bias + W[:, W : W + ninp] x_t: the input columns as up to four fp32 MFMA k-steps (x[] is zero past ninp)
-template <int KT>
-__device__ __forceinline__ void lwt_tile_init(const LemWideTrainArgs& a, int g, int ct, int lane, int hh, int ns, const float (&x)[8], f32x16& acc) {
+// acc (tile ct) = bias + W[:, W : W + ninp] x_t: the input columns as ceil(ninp / 2) fp32 MFMA k-steps (the pad of an odd ninp is zero).
+// NS > 0: that many steps, x[s] = feature 2 s + hh of the lane's node.  NS = 0: `ns` steps, x[f] = feature f (zero past the stride).
+template <int KT, int NS>
+__device__ __forceinline__ void lwt_tile_init(const LemWideTrainArgs& a, int g, int ct, int lane, int hh, int ns, const float (&x)[NS ? NS : 8], f32x16& acc) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const f32x4 bv = *reinterpret_cast<const f32x4*>(a.bias + (g * KT + ct) * 32 + 8 * q + 4 * hh);
@@ -230,24 +251,30 @@ __device__ __forceinline__ void lwt_tile_init(const LemWideTrainArgs& a, int g, 
     }
     const float* wf = a.wx + (size_t)(g * KT + ct) * 256 + lane;
 #pragma unroll
-    for (int s = 0; s < 4; ++s)
-        if (s < ns) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[s * 64], hh ? x[2 * s + 1] : x[2 * s], acc, 0, 0, 0);
+    for (int s = 0; s < (NS ? NS : 4); ++s) {
+        if constexpr (NS != 0) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[s * 64], x[s], acc, 0, 0, 0);
+        else if (s < ns) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[s * 64], hh ? x[2 * s + 1] : x[2 * s], acc, 0, 0, 0);
+    }
 }
 
-template <int KT>
-__global__ __launch_bounds__(64 * KT) void lem_wide_train_fwd_kernel(LemWideTrainArgs a) {
+// The forward.  NS = 0: the input stride is a.stride, read at run time.  NS > 0 (KT = 4, the flagship width, only): it is a compile-time
+// constant of the whole body and the kernel below branches on it once.  At run time the step-input loads and the input-column MFMAs of every
+// step sit behind branches, which at width 128 cost the forward 5 % (51 200 nodes) to 13 % (1 600 nodes) against the retired 128-wide kernel,
+// whose NS was a template argument too (profiles/r19a_one_lem_training_pair.md).  The other KT keep the run-time body: with four bodies per
+// kernel they would hold 167 - 176 registers instead of 149 - 160 and lose a workgroup per CU.
+template <int KT, int NS>
+__device__ __forceinline__ void lwt_forward(const LemWideTrainArgs& a, u32x4* xf) {
     constexpr int WP = 32 * KT;
-    __shared__ u32x4 xf[KT * LWT_KTILE_U4];                          // 6 KT KB: y, then z', alternately
     const int tid = threadIdx.x, lane = tid & 63;
     const int ct = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int c = lane & 31, hh = lane >> 5, W = a.width, ns = a.stride >> 1;
+    const int c = lane & 31, hh = lane >> 5, W = a.width, stride = NS ? 2 * NS : a.stride, ns = stride >> 1;
     const size_t plane = (size_t)a.n_nodes * a.t_len * WP;
     const __amdgpu_buffer_rsrc_t stream = lwt_stream<KT>(a.rec, ct);
     const long n = (long)blockIdx.x * 32 + c;
     const bool live = n < a.n_nodes;
     const long nc = live ? n : a.n_nodes - 1;
     const bool save = live && a.saved != nullptr;
-    const float* xrow = a.xin + (size_t)nc * a.t_len * a.stride;
+    const float* xrow = a.xin + (size_t)nc * a.t_len * stride + (NS ? hh : 0);
     float* srow = a.saved + (size_t)nc * a.t_len * WP + 4 * hh;
 
     f32x16 y, z, g, acc;
@@ -263,18 +290,27 @@ __global__ __launch_bounds__(64 * KT) void lem_wide_train_fwd_kernel(LemWideTrai
     __syncthreads();
 
     for (int t = 0; t < a.t_len; ++t) {
-        float x[8];
+        float x[NS ? NS : 8];
 #pragma unroll
-        for (int f = 0; f < 8; ++f) x[f] = f < a.stride ? xrow[(size_t)t * a.stride + f] : 0.f;
+        for (int f = 0; f < (NS ? NS : 8); ++f) {
+            if constexpr (NS != 0) x[f] = xrow[(size_t)t * stride + 2 * f];
+            else x[f] = f < stride ? xrow[(size_t)t * stride + f] : 0.f;
+        }
         float* st = srow + (size_t)t * WP;
+        // NS > 0: the input-column fragments are the same in every step; read through an offset the compiler cannot see through, they are
+        // loaded where they are used (L1 hits) instead of being held in 4 NS registers for the whole loop: a body alone needs at most 164
+        // registers, not 176, and the kernel of the four bodies 168, which is three workgroups per CU instead of two (with two, the forward
+        // with saving of 51 200 nodes took 1.74 ms, not 1.63)
+        int wlane = lane;
+        if constexpr (NS != 0) asm volatile("" : "+v"(wlane));
 
         if (save) lwt_tile_store(st + LWT_Y * plane, ct, y);        // y_{t-1}, the state ENTERING the step
-        lwt_tile_init<KT>(a, 0, ct, lane, hh, ns, x, g);             // g2 -> a2            (published: y)
+        lwt_tile_init<KT, NS>(a, 0, ct, wlane, hh, ns, x, g);             // g2 -> a2            (published: y)
         lwt_gemm<KT, 0>(wA, wB, stream, xf, lane, loff, g);
 #pragma unroll
         for (int r = 0; r < 16; ++r) g[r] = a.dt * sigmoidf_(g[r]);
         if (save) lwt_tile_store(st + LWT_A2 * plane, ct, g);
-        lwt_tile_init<KT>(a, 1, ct, lane, hh, ns, x, acc);           // g3 -> c, z'
+        lwt_tile_init<KT, NS>(a, 1, ct, wlane, hh, ns, x, acc);           // g3 -> c, z'
         lwt_gemm<KT, 1>(wA, wB, stream, xf, lane, loff, acc);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -285,14 +321,14 @@ __global__ __launch_bounds__(64 * KT) void lem_wide_train_fwd_kernel(LemWideTrai
             lwt_tile_store(st + LWT_C * plane, ct, acc);
             lwt_tile_store(st + LWT_Z * plane, ct, z);
         }
-        lwt_tile_init<KT>(a, 2, ct, lane, hh, ns, x, g);             // g1 -> a1
+        lwt_tile_init<KT, NS>(a, 2, ct, wlane, hh, ns, x, g);             // g1 -> a1
         lwt_gemm<KT, 2>(wA, wB, stream, xf, lane, loff, g);
         __syncthreads();                                             // every wave has read the last fragment of y
 #pragma unroll
         for (int r = 0; r < 16; ++r) g[r] = a.dt * sigmoidf_(g[r]);
         if (save) lwt_tile_store(st + LWT_A1 * plane, ct, g);
         lwt_publish(xf, ct, lane, z);
-        lwt_tile_init<KT>(a, 3, ct, lane, hh, ns, x, acc);           // lin -> d, y'        (published: z')
+        lwt_tile_init<KT, NS>(a, 3, ct, wlane, hh, ns, x, acc);           // lin -> d, y'        (published: z')
         __syncthreads();
         lwt_gemm<KT, 3>(wA, wB, stream, xf, lane, loff, acc);
         __syncthreads();                                             // every wave has read the last fragment of z'
@@ -308,6 +344,21 @@ __global__ __launch_bounds__(64 * KT) void lem_wide_train_fwd_kernel(LemWideTrai
     if (live) {
         lwt_dense_store(a.y_out + (size_t)n * W, ct, hh, W, y);
         if (a.z_out) lwt_dense_store(a.z_out + (size_t)n * W, ct, hh, W, z);
+    }
+}
+
+template <int KT>
+__global__ __launch_bounds__(64 * KT) void lem_wide_train_fwd_kernel(LemWideTrainArgs a) {
+    __shared__ u32x4 xf[KT * LWT_KTILE_U4];                          // 6 KT KB: y, then z', alternately
+    if constexpr (KT == 4) {
+        switch (a.stride >> 1) {
+            case 1: lwt_forward<KT, 1>(a, xf); break;
+            case 2: lwt_forward<KT, 2>(a, xf); break;
+            case 3: lwt_forward<KT, 3>(a, xf); break;
+            default: lwt_forward<KT, 4>(a, xf); break;
+        }
+    } else {
+        lwt_forward<KT, 0>(a, xf);
     }
 }
 

@@ -31,45 +31,31 @@ class LEMcuda(nn.Module):
         self._wide_train_blob = PackedCache()
         self.reset_parameters()
 
-    def _pack_wide(self):
-        """The blob of msmp_lem_encoder_wide_f32, cached like LEM._pack (PackedCache)."""
+    def _pack(self, cache, size_entry, pack_entry):
+        """A blob of the four parameters, `size_entry(ninp, nhid)` floats written by `pack_entry`, cached like LEM._pack (PackedCache)."""
         ps = [self.weights, self.weights_lin_z, self.bias, self.bias_lin_z]
 
         def build():
             L = lib()
-            n_floats = L.msmp_packed_lem_wide_floats(self.ninp, self.nhid)
+            n_floats = getattr(L, size_entry)(self.ninp, self.nhid)
             if n_floats <= 0:
-                check(MSMP_ERR_UNSUPPORTED, 'msmp_packed_lem_wide_floats')
+                check(MSMP_ERR_UNSUPPORTED, size_entry)
             blob = torch.empty(n_floats, dtype=torch.float32, device=ps[0].device)
             f = [p.detach().to(torch.float32).contiguous() for p in ps]
-            check(L.msmp_pack_lem_wide_f32(*[ptr(t) for t in f], self.ninp, self.nhid, ptr(blob), current_stream()), 'msmp_pack_lem_wide_f32')
+            check(getattr(L, pack_entry)(*[ptr(t) for t in f], self.ninp, self.nhid, ptr(blob), current_stream()), pack_entry)
             return blob
-        return self._wide_blob.get(ps, build)
+        return cache.get(ps, build)
+
+    def _pack_wide(self):
+        """The blob of msmp_lem_encoder_wide_f32 (fp16-split fragments)."""
+        return self._pack(self._wide_blob, 'msmp_packed_lem_wide_floats', 'msmp_pack_lem_wide_f32')
 
     def _pack_wide_train(self):
-        """The forward blob of msmp_lem_train_fwd_wide_f32 (bf16x3 fragments), cached like _pack_wide."""
-        ps = [self.weights, self.weights_lin_z, self.bias, self.bias_lin_z]
-
-        def build():
-            L = lib()
-            n_floats = L.msmp_packed_lem_wide_train_floats(self.ninp, self.nhid)
-            if n_floats <= 0:
-                check(MSMP_ERR_UNSUPPORTED, 'msmp_packed_lem_wide_train_floats')
-            blob = torch.empty(n_floats, dtype=torch.float32, device=ps[0].device)
-            f = [p.detach().to(torch.float32).contiguous() for p in ps]
-            check(L.msmp_pack_lem_wide_train_f32(*[ptr(t) for t in f], self.ninp, self.nhid, ptr(blob), current_stream()), 'msmp_pack_lem_wide_train_f32')
-            return blob
-        return self._wide_train_blob.get(ps, build)
-
-    def wide_train_selected(self, xin):
-        """True where a forward under autograd runs on the width-generic training kernels (_LEMWideTrainFunction): grad enabled, some
-        parameter requires grad, fp32 parameters and inputs on the GPU, at least one node, msmp_tune "lem_wide_train" not 0."""
-        return (torch.is_grad_enabled() and xin.is_cuda and xin.dtype == torch.float32 and xin.shape[0] > 0 and self.wide_kernel_exists()
-                and all(p.dtype == torch.float32 and p.is_cuda for p in self.parameters()) and any(p.requires_grad for p in self.parameters())
-                and lib().msmp_tune_query(b'lem_wide_train') != 0)
+        """The forward blob of msmp_lem_train_fwd_wide_f32 (bf16x3 fragments)."""
+        return self._pack(self._wide_train_blob, 'msmp_packed_lem_wide_train_floats', 'msmp_pack_lem_wide_train_f32')
 
     def wide_kernel_exists(self):
-        """True at the sizes msmp_lem_encoder_wide_f32 takes."""
+        """True at the sizes msmp_lem_encoder_wide_f32 and the training pair take."""
         return 1 <= self.ninp <= 8 and 1 <= self.nhid <= 256
 
     def wide_kernel_selected(self):
@@ -142,59 +128,9 @@ def _state(t):
     return None if t is None else t.detach().to(torch.float32).contiguous()
 
 
-def _train_forward(owner, x, ninp, y0, z0, saved):
-    """msmp_lem_train_fwd_f32: the exact-fp32 recurrence from the states (y0, z0) (None = zeros) -> (y_T, z_T)."""
-    n, t_len = x.shape[0], x.shape[1]
-    out = torch.empty(n, owner.nhid, dtype=torch.float32, device=x.device)
-    z_out = torch.empty_like(out)
-    check(lib().msmp_lem_train_fwd_f32(ptr(x), n, t_len, ninp, owner.rnn.dt, ptr(owner._pack(None)), ptr(y0), ptr(z0), ptr(saved),
-                                       ptr(out), ptr(z_out), current_stream()), 'msmp_lem_train_fwd_f32')
-    return out, z_out
-
-
-class _LEMTrainFunction(torch.autograd.Function):
-    """LEMFunction of the reference (experiments/models_gnn.py:285-302) on the HIP training kernels: forward =
-    msmp_lem_train_fwd_f32 (saves the per-step activations), backward = msmp_lem_train_bwd_f32 (BPTT, one launch) followed
-    by the weight-gradient GEMMs over the N*T rows.  Like the reference it returns no gradient for the step inputs."""
-
-    @staticmethod
-    def forward(ctx, owner, xin, weights, weights_lin_z, bias, bias_lin_z, y0=None, z0=None):
-        x = _padded_inputs(xin)
-        n, t_len, ninp = xin.shape
-        saved = torch.empty(lib().msmp_lem_saved_floats(n, t_len), dtype=torch.float32, device=x.device)
-        y0, z0 = _state(y0), _state(z0)
-        out, z_out = _train_forward(owner, x, ninp, y0, z0, saved)
-        ctx.save_for_backward(x, saved, weights, weights_lin_z, *([y0, z0] if y0 is not None else []))
-        ctx.dt, ctx.ninp = owner.rnn.dt, ninp
-        ctx.mark_non_differentiable(z_out)          # the carried state: a constant for the next call (models_gnn.py:350-353)
-        return out, z_out
-
-    @staticmethod
-    def backward(ctx, grad_y, _grad_z=None):
-        L = lib()
-        x, saved, weights, weights_lin_z, *states = ctx.saved_tensors
-        y0, z0 = states if states else (None, None)
-        n, t_len, stride = x.shape
-        nh = weights_lin_z.shape[0]
-        blob = torch.empty(L.msmp_packed_lem_bwd_floats(), dtype=torch.float32, device=x.device)
-        w, wz = (p.detach().to(torch.float32).contiguous() for p in (weights, weights_lin_z))
-        check(L.msmp_pack_lem_bwd_f32(ptr(w), ptr(wz), ctx.ninp, ptr(blob), current_stream()), 'msmp_pack_lem_bwd_f32')
-        dg = torch.empty(n * t_len, 4 * nh, dtype=torch.float32, device=x.device)
-        g = grad_y.to(torch.float32).contiguous()
-        check(L.msmp_lem_train_bwd_f32(ptr(g), ptr(saved), ptr(y0), ptr(z0), n, t_len, ctx.dt, ptr(blob), ptr(dg), current_stream()),
-              'msmp_lem_train_bwd_f32')
-        planes = saved.view(6, n, t_len, nh)
-        xs = x.view(n * t_len, stride)[:, :ctx.ninp]
-        y_prev = planes[4].reshape(n * t_len, nh)            # the forward saves y_{t-1} (y0 at t = 0): the rows of [y_{t-1} ; x_t]
-        z_new = planes[5].reshape(n * t_len, nh)
-        from .autograd import grad_weights          # weight / bias gradients: sums over the N*T rows; [state | x_t] is never materialised
-        g = grad_weights([(dg[:, :nh], y_prev, xs), (dg[:, nh:2 * nh], y_prev, xs), (dg[:, 2 * nh:3 * nh], y_prev, xs), (dg[:, 3 * nh:], z_new, xs)])
-        d_w, d_b = torch.cat(g[0:6:2], 0), torch.cat(g[1:6:2], 0)
-        return None, None, d_w.to(weights.dtype), g[6].to(weights_lin_z.dtype), d_b, g[7], None, None
-
-
-def _wide_train_forward(rnn, x, y0, z0, saved):
-    """msmp_lem_train_fwd_wide_f32: the fp32-exact recurrence at any width from the states (y0, z0) (None = zeros) -> (y_T, z_T)."""
+def _train_forward(rnn, x, y0, z0, saved=None):
+    """msmp_lem_train_fwd_wide_f32: the fp32-exact recurrence at any width from the states (y0, z0) (None = zeros) -> (y_T, z_T); `saved`: the
+    planes the backward reads (msmp_lem_wide_saved_floats), or None when no backward follows."""
     n, t_len = x.shape[0], x.shape[1]
     out = torch.empty(n, rnn.nhid, dtype=torch.float32, device=x.device)
     z_out = torch.empty_like(out)
@@ -203,11 +139,11 @@ def _wide_train_forward(rnn, x, y0, z0, saved):
     return out, z_out
 
 
-class _LEMWideTrainFunction(torch.autograd.Function):
-    """_LEMTrainFunction at any hidden width 1..256 (the GLU classes: 164): forward = msmp_lem_train_fwd_wide_f32, backward =
-    msmp_lem_train_bwd_wide_f32 followed by ONE msmp_grad_weights_cat_f32 call whose jobs are the 128-column blocks of the four gates
-    of dG (at most 8).  Allocates through torch only and never synchronises (hipGraph capture).  No gradient for the step inputs or the
-    initial states, as at 128."""
+class _LEMTrainFunction(torch.autograd.Function):
+    """LEMFunction of the reference (experiments/models_gnn.py:285-302) on the HIP training kernels at any hidden width 1..256: forward =
+    msmp_lem_train_fwd_wide_f32 (saves the per-step activations), backward = msmp_lem_train_bwd_wide_f32 (BPTT, one launch) followed by ONE
+    msmp_grad_weights_cat_f32 call whose jobs are the 128-column blocks of the four gates of dG (at most 8).  Allocates through torch only and
+    never synchronises (hipGraph capture).  Like the reference it returns no gradient for the step inputs, nor for the initial states."""
 
     @staticmethod
     def forward(ctx, rnn, xin, weights, weights_lin_z, bias, bias_lin_z, y0=None, z0=None):
@@ -215,10 +151,10 @@ class _LEMWideTrainFunction(torch.autograd.Function):
         n, t_len, _ = xin.shape
         saved = torch.empty(lib().msmp_lem_wide_saved_floats(n, t_len, rnn.nhid), dtype=torch.float32, device=x.device)
         y0, z0 = _state(y0), _state(z0)
-        out, z_out = _wide_train_forward(rnn, x, y0, z0, saved)
+        out, z_out = _train_forward(rnn, x, y0, z0, saved)
         ctx.save_for_backward(x, saved, weights, weights_lin_z, *([y0, z0] if y0 is not None else []))
         ctx.dt, ctx.ninp = rnn.dt, rnn.ninp
-        ctx.mark_non_differentiable(z_out)
+        ctx.mark_non_differentiable(z_out)          # the carried state: a constant for the next call (models_gnn.py:350-353)
         return out, z_out
 
     @staticmethod
@@ -238,27 +174,27 @@ class _LEMWideTrainFunction(torch.autograd.Function):
               'msmp_lem_train_bwd_wide_f32')
         planes = saved.view(6, n * t_len, wp)
         xs = x.view(n * t_len, stride)[:, :ninp]
-        y_prev, z_new = planes[4][:, :nh], planes[5][:, :nh]
-        from .autograd import grad_weights
+        y_prev, z_new = planes[4][:, :nh], planes[5][:, :nh]        # the forward saves y_{t-1} (y0 at t = 0): the rows of [y_{t-1} ; x_t]
+        from .autograd import grad_weights          # weight / bias gradients: sums over the N*T rows; [state | x_t] is never materialised
         jobs = [(dg[:, gate * ldg + 128 * j:gate * ldg + 128 * (j + 1)], z_new if gate == 3 else y_prev, xs) for gate in range(4) for j in range(nblk)]
         r = grad_weights(jobs)
-        gate_w = [torch.cat(r[2 * nblk * gate:2 * nblk * (gate + 1):2], 0)[:nh] for gate in range(4)]       # rows >= width of a block: zero columns of dG
-        gate_b = [torch.cat(r[2 * nblk * gate + 1:2 * nblk * (gate + 1):2], 0)[:nh] for gate in range(4)]
-        return (None, None, torch.cat(gate_w[:3], 0).to(weights.dtype), gate_w[3].to(weights_lin_z.dtype), torch.cat(gate_b[:3], 0), gate_b[3],
-                None, None)
 
+        def rows(kind, gates):          # kind 0: weight, 1: bias blocks of `gates`, without the rows >= width of a last block (zero columns of dG)
+            blocks = [r[2 * (nblk * gate + j) + kind][:min(128, nh - 128 * j)] for gate in gates for j in range(nblk)]
+            return blocks[0] if len(blocks) == 1 else torch.cat(blocks, 0)
+        return (None, None, rows(0, (0, 1, 2)).to(weights.dtype), rows(0, (3,)).to(weights_lin_z.dtype), rows(1, (0, 1, 2)), rows(1, (3,)), None, None)
+
+
+_LEMWideTrainFunction = _LEMTrainFunction       # its name while a 128-wide Function stood beside it: the test suite of that revision, run against this library, imports it
 
 class LEM(nn.Module):
     """experiments/models_gnn.py:333-342: returns all_y[-1].
 
-    `forward` is the differentiable path: the HIP training kernels (_LEMTrainFunction at width 128; at any other width
-    _LEMWideTrainFunction while msmp_tune "lem_wide_train" is not 0, some LEM parameter requires grad and module and inputs are fp32, else
-    the PyTorch-ROCm restatement).  There is NO CPU path: host tensors
-    raise.  TRAIN_KERNELS = False is a validation aid only (scripts/train_soak.py, scripts/train_step_time.py): it routes GPU
-    tensors through the PyTorch-ROCm restatement `LEMcuda.forward`, which the tests also call directly in float64 as the
-    reference of the kernels.  `encode` /
-    `encode_nodes` are the product path for inference: the fused HIP kernel (recurrence + lemoutput_mlp in one launch,
-    states in registers)."""
+    `forward` / `forward_nodes` are the differentiable path; `_recurrence` is where they are routed (the table is in its docstring).  There
+    is NO CPU path: host tensors raise.  TRAIN_KERNELS = False is a validation aid only (scripts/train_soak.py, scripts/train_step_time.py):
+    under autograd it routes GPU tensors through the PyTorch-ROCm restatement `LEMcuda.forward`, which the tests also call directly in
+    float64 as the reference of the kernels.  `encode` / `encode_nodes` are the product path for inference at width 128: the fused HIP
+    kernel (recurrence + lemoutput_mlp in one launch, states in registers)."""
     TRAIN_KERNELS = True
 
     def __init__(self, ninp, nhid, dt=1.):
@@ -273,19 +209,36 @@ class LEM(nn.Module):
 
     def forward_nodes(self, xin):
         """Same with node-major step inputs xin [N, T, ninp] (the layout the kernels read)."""
+        return self._recurrence(xin, None)[0]
+
+    def _recurrence(self, xin, states):
+        """xin [N, T, ninp], states = (y0, z0) or None (zeros) -> (y_T, z_T).  The one place where LEM and LEMS choose a path.  With
+        "native" = module fp32 on the GPU, inputs fp32 (at width 128 any dtype: they are cast), N > 0, ninp <= 8, width <= 256, and
+        "backward" = grad enabled and a parameter requires grad:
+
+            native, backward, TRAIN_KERNELS, msmp_tune "lem_wide_train" != 0   _LEMTrainFunction (msmp_lem_train_fwd_wide_f32 with `saved`, then
+                                                                               msmp_lem_train_bwd_wide_f32 + msmp_grad_weights_cat_f32)
+            native, no backward, width 128                                     msmp_lem_train_fwd_wide_f32 with saved = NULL: fp32-exact and it takes
+                                                                               initial states (the weight-stationary inference kernel does neither)
+            other widths, no grad, fp32 module, N > 0, wide_kernel_selected()  LEMcuda.forward_wide: msmp_lem_encoder_wide_f32 on xin as it is
+            everything else                                                    LEMcuda.forward: without grad the GEMM + pointwise loop; under
+                                                                               autograd (switch 0, TRAIN_KERNELS = False, float64) the PyTorch-ROCm
+                                                                               restatement of the cell
+        """
         if not xin.is_cuda:
-            raise RuntimeError('LEM needs CUDA tensors; there is no CPU fallback')
-        if self.nhid != 128:            # the GLU classes (164 hidden units): no grad = the width-generic HIP kernel, training = its bf16x3 pair, else the PyTorch-ROCm restatement of the cell
-            if not torch.is_grad_enabled() and xin.shape[0] > 0 and self.rnn.weights.dtype == torch.float32 and self.rnn.wide_kernel_selected():
-                return self.rnn.forward_wide(xin)[0]
-            if self.TRAIN_KERNELS and self.rnn.wide_train_selected(xin):
-                r = self.rnn
-                return _LEMWideTrainFunction.apply(r, xin, r.weights, r.weights_lin_z, r.bias, r.bias_lin_z)[0]
-            return self.rnn(xin.permute(1, 0, 2).contiguous().to(self.rnn.weights.dtype))
-        if not self.TRAIN_KERNELS:
-            return self.rnn(xin.permute(1, 0, 2).contiguous())
+            raise RuntimeError(f'{type(self).__name__} needs CUDA tensors; there is no CPU fallback')
         r = self.rnn
-        return _LEMTrainFunction.apply(self, xin, r.weights, r.weights_lin_z, r.bias, r.bias_lin_z)[0]
+        y0, z0 = states if states is not None else (None, None)
+        fp32_module = all(p.dtype == torch.float32 and p.is_cuda for p in r.parameters())
+        if (xin.dtype == torch.float32 or self.nhid == 128) and xin.shape[0] > 0 and r.wide_kernel_exists() and fp32_module:
+            if torch.is_grad_enabled() and any(p.requires_grad for p in r.parameters()):
+                if self.TRAIN_KERNELS and lib().msmp_tune_query(b'lem_wide_train') != 0:
+                    return _LEMTrainFunction.apply(r, xin, r.weights, r.weights_lin_z, r.bias, r.bias_lin_z, y0, z0)
+            elif self.nhid == 128:
+                return _train_forward(r, _padded_inputs(xin), _state(y0), _state(z0))
+        if self.nhid != 128 and not torch.is_grad_enabled() and xin.shape[0] > 0 and fp32_module and r.wide_kernel_selected():
+            return r.forward_wide(xin, states)
+        return r(xin.permute(1, 0, 2).contiguous().to(r.weights.dtype), states, return_state=True)
 
     def _pack(self, mlp):
         ps = [self.rnn.weights, self.rnn.weights_lin_z, self.rnn.bias, self.rnn.bias_lin_z]
@@ -336,11 +289,7 @@ class LEM(nn.Module):
 class LEMS(LEM):
     """experiments/models_gnn.py:345-362: the LEM that keeps (all_y[-1], all_z[-1]) of a call as the initial states of the next
     (`reset_states()` starts a new unrolling sequence; train_helper.py:144-145, 199-200).  The carried states are constants for
-    the next call.  At width 128 it runs on the exact-fp32 recurrence kernel (msmp_lem_train_fwd_f32; with autograd its BPTT pair), which
-    takes initial states; the weight-stationary inference kernel starts from zeros and is not used here.  At any other width: without
-    grad LEMcuda.forward's inference branch (msmp_lem_encoder_wide_f32, or the GEMM loop under msmp_tune "lem_wide" 0 / exact fp32), with
-    grad the width-generic training pair (_LEMWideTrainFunction: msmp_lem_train_fwd_wide_f32 / _bwd_wide_f32, which take initial states) or,
-    under msmp_tune "lem_wide_train" 0, TRAIN_KERNELS = False or in float64, the PyTorch-ROCm restatement; all with the carried states."""
+    the next call.  Same routes as LEM (LEM._recurrence), all of which take initial states."""
 
     def __init__(self, ninp, nhid, dt=1.):
         super().__init__(ninp, nhid, dt)
@@ -349,26 +298,8 @@ class LEMS(LEM):
     def reset_states(self):
         self.states = None
 
-    def forward(self, inputs):
-        return self.forward_nodes(inputs.permute(1, 0, 2))
-
     def forward_nodes(self, xin):
-        y0, z0 = self.states if self.states is not None else (None, None)
-        r = self.rnn
-        if not xin.is_cuda:
-            raise RuntimeError('LEMS needs CUDA tensors (HIP path only, no CPU fallback)')
-        if self.nhid != 128:
-            if self.TRAIN_KERNELS and r.wide_train_selected(xin):
-                y, z = _LEMWideTrainFunction.apply(r, xin, r.weights, r.weights_lin_z, r.bias, r.bias_lin_z, y0, z0)
-            else:
-                y, z = r(xin.permute(1, 0, 2).contiguous().to(r.weights.dtype), None if y0 is None else (y0, z0), return_state=True)
-        elif torch.is_grad_enabled() and any(p.requires_grad for p in r.parameters()):
-            if self.TRAIN_KERNELS:
-                y, z = _LEMTrainFunction.apply(self, xin, r.weights, r.weights_lin_z, r.bias, r.bias_lin_z, y0, z0)
-            else:
-                y, z = r(xin.permute(1, 0, 2).contiguous(), None if y0 is None else (y0, z0), return_state=True)
-        else:
-            y, z = _train_forward(self, _padded_inputs(xin), xin.shape[2], _state(y0), _state(z0), None)
+        y, z = self._recurrence(xin, self.states)
         self.states = (y.detach(), z.detach())
         return y
 

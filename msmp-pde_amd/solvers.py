@@ -260,23 +260,17 @@ class _SolverBase(nn.Module):
             if torch.is_grad_enabled() and any(p.requires_grad for p in self.embedding_mlp.parameters()):
                 return self.embedding_mlp(torch.cat((u, pos_x, variables), -1))      # differentiable PyTorch path
             return self._embed_hip(u, pos_x, variables)
-        if isinstance(self.embedding_lem, LEMS):       # stateful encoder: always the state-taking recurrence kernel
-            return self.lemoutput_mlp(self.embedding_lem.forward_nodes(self._step_inputs(u, pos_x, pos_t, variables, dt)))
-        if self.hidden_features != 128:     # the GLU classes (any width; lem.LEM.forward_nodes): no grad = the width-generic HIP recurrence + two HIP row GEMMs
-            y = self.embedding_lem.forward_nodes(self._step_inputs(u, pos_x, pos_t, variables, dt))
-            if not torch.is_grad_enabled() and y.dtype == torch.float32 and self.embedding_lem.rnn.wide_kernel_selected():
-                return lemoutput_mlp(self.lemoutput_mlp, y)
-            return self.lemoutput_mlp(y)
-        grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.embedding_lem.parameters())
-        if not grad:                    # step inputs assembled inside the kernel (no [N, T, ninp] tensor)
-            h = self.embedding_lem.encode_nodes(u, pos_x, pos_t, variables, dt, self.TWO_D, self.lemoutput_mlp)
-            if h is not None:
-                return h
-        lem_in = self._step_inputs(u, pos_x, pos_t, variables, dt)
-        if grad:
-            h = self.embedding_lem.forward_nodes(lem_in)       # HIP training kernels (recurrence forward + BPTT)
-            return self.lemoutput_mlp(h)
-        return self.embedding_lem.encode(lem_in, self.lemoutput_mlp)       # fused HIP kernel (recurrence + MLP)
+        lem = self.embedding_lem
+        stateless = not isinstance(lem, LEMS)
+        grad = torch.is_grad_enabled() and any(p.requires_grad for p in lem.parameters())
+        if stateless and self.hidden_features == 128 and not grad:      # 128-wide inference: the fused HIP kernel (recurrence + MLP)
+            h = lem.encode_nodes(u, pos_x, pos_t, variables, dt, self.TWO_D, self.lemoutput_mlp)     # step inputs assembled inside the kernel (no [N, T, ninp] tensor)
+            return h if h is not None else lem.encode(self._step_inputs(u, pos_x, pos_t, variables, dt), self.lemoutput_mlp)
+        y = lem.forward_nodes(self._step_inputs(u, pos_x, pos_t, variables, dt))       # lem.LEM._recurrence: training kernels, state-taking recurrence or restatement
+        if (stateless and self.hidden_features != 128 and not torch.is_grad_enabled() and y.dtype == torch.float32
+                and lem.rnn.wide_kernel_selected()):       # the GLU classes without grad: the width-generic HIP recurrence + two HIP row GEMMs
+            return lemoutput_mlp(self.lemoutput_mlp, y)
+        return self.lemoutput_mlp(y)
 
     def _step_inputs(self, u, pos_x, pos_t, variables, dt):
         """The recurrent encoder's per-step inputs, node-major [N, T, ninp]."""

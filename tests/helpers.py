@@ -294,6 +294,15 @@ def oracle_layer(main, gate, args, ei, batch):
     return (1.0 - tau) * args64[0] + tau * O.swish(ref)
 
 
+def abi_versions_agree(header, L):
+    """True when the ABI version is one number in its three places: the #define of include/msmp_pde.h (`header`: its text),
+    msmp_version() of the built library `L`, and the constant the ctypes binding refuses other libraries by."""
+    import re
+    from msmp_pde_amd._lib import MSMP_ABI_VERSION
+    define = re.search(r'#define\s+MSMP_ABI_VERSION\s+(\d+)\b', header)
+    return bool(define) and int(define.group(1)) == L.msmp_version() == MSMP_ABI_VERSION
+
+
 def counted(mp, monkeypatch, name):
     """the list that grows by one entry per call of the C-ABI entry `name` from here on (until monkeypatch undoes it)"""
     L = mp.lib()

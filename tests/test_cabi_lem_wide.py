@@ -9,6 +9,8 @@ import sys
 
 import pytest
 
+from helpers import abi_versions_agree
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'msmp-pde_amd', 'csrc')
 HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
@@ -30,7 +32,7 @@ def test_header_declares_and_library_exports_the_entry(L):
     for name in NAMES:
         assert re.search(r'\b' + name + r'\s*\(', header), name
         assert getattr(L, name) is not None
-    assert re.search(r'#define\s+MSMP_ABI_VERSION\s+410\b', header) and L.msmp_version() == 410
+    assert abi_versions_agree(header, L)
 
 
 @pytest.mark.parametrize('width,kt', [(1, 1), (32, 1), (33, 2), (96, 3), (128, 4), (164, 6), (192, 6), (256, 8)])

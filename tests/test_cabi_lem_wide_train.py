@@ -1,16 +1,19 @@
-"""CPU tests (no kernel launched) of the width-generic LEM TRAINING entries (lem_wide_train_kernel.hip): the header declares them, the built
-library exports them with the signatures the ctypes binding lists, the size entries follow the documented formulas and refuse shapes
-outside the range, pack and launch entries refuse null pointers by return value, and the switch "lem_wide_train" is documented, listed
-and stores the value it is given."""
+"""CPU tests (no kernel launched) of the LEM TRAINING entries (lem_wide_train_kernel.hip, every width 1 .. 256): the header declares them, the
+built library exports them with the signatures the ctypes binding lists, the size entries follow the documented formulas and refuse shapes
+outside the range, pack and launch entries refuse null pointers by return value, the switch "lem_wide_train" is documented, listed
+and stores the value it is given, and the retired 128-wide entries and their section of the inference blob are gone."""
 import os
 import re
 import sys
 
 import pytest
 
+from helpers import abi_versions_agree
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ('msmp_packed_lem_wide_train_floats', 'msmp_pack_lem_wide_train_f32', 'msmp_packed_lem_wide_bwd_floats', 'msmp_pack_lem_wide_bwd_f32',
          'msmp_lem_wide_saved_floats', 'msmp_lem_wide_dg_floats', 'msmp_lem_train_fwd_wide_f32', 'msmp_lem_train_bwd_wide_f32')
+RETIRED = ('msmp_lem_saved_floats', 'msmp_lem_train_fwd_f32', 'msmp_packed_lem_bwd_floats', 'msmp_pack_lem_bwd_f32', 'msmp_lem_train_bwd_f32')
 
 
 def _header():
@@ -37,7 +40,23 @@ def test_header_declares_and_library_exports_the_entries(L):
         n_args = 0 if protos[0].strip() == 'void' else len(protos[0].split(','))
         assert getattr(L, name) is not None
         assert len(SIGNATURES[name][1]) == n_args, (name, n_args)
-    assert re.search(r'#define\s+MSMP_ABI_VERSION\s+410\b', header) and L.msmp_version() == 410
+    assert abi_versions_agree(header, L)
+
+
+def test_the_128_wide_entries_are_retired(L):
+    """The five entries of the 128-wide pair are in neither the header, the binding's table nor the built library, and the blob of
+    msmp_pack_lem_f32 is the sum of its remaining sections (the bf16x3 copy of the recurrent chunks, which only that pair read, is gone)."""
+    from msmp_pde_amd._lib import SIGNATURES
+    header = _header()
+    for name in RETIRED:
+        assert not re.search(r'\b' + name + r'\b', header), name
+        assert name not in SIGNATURES, name
+        assert not hasattr(L, name), name
+    chunk, h, max_inp = 128 * 32, 128, 8
+    fp32 = 16 * chunk + 8 * chunk + 4 * h + 4 * h * max_inp + 2 * h       # rec | mlp | bias | wx | mlp bias
+    split = 8 + fp32                                                      # scales | the same five, fp16-split
+    wx_h = 4 * 4 * 2 * 64 * 8 // 2                                        # input columns as fp16 slot fragments
+    assert L.msmp_packed_lem_floats() == fp32 + split + wx_h == 214536
 
 
 @pytest.mark.parametrize('width,kt,blk', [(33, 2, 1), (128, 4, 1), (129, 5, 2), (164, 6, 2), (256, 8, 2)])

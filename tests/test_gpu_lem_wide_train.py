@@ -1,10 +1,13 @@
-"""GPU tests of the width-generic LEM TRAINING pair (lem_wide_train_kernel.hip: msmp_lem_train_fwd_wide_f32 / msmp_lem_train_bwd_wide_f32) and of its
-host route (lem._LEMWideTrainFunction): parity with the float64 restatement of the cell (LEMcuda.forward) at the bars of the same arithmetic at
-width 128 (test_lem_training_kernels_match_float64_restatement: 1e-5 absolute on the states, 1e-4 of the largest entry of each gradient
-tensor), bitwise properties, memory discipline, the absence of an input range, argument errors, the host routes, two solver classes against
-the float64 oracle, and hipGraph capture.  Every test sets the switch "lem_wide_train" itself."""
+"""GPU tests of the LEM TRAINING pair (lem_wide_train_kernel.hip: msmp_lem_train_fwd_wide_f32 / msmp_lem_train_bwd_wide_f32, every width 1 .. 256) and
+of its host route (lem._LEMTrainFunction, lem.LEM._recurrence): parity with the float64 restatement of the cell (LEMcuda.forward) at the bars of
+test_lem_training_kernels_match_float64_restatement (1e-5 absolute on the states, 1e-4 of the largest entry of each gradient tensor), the bits
+of the retired 128-wide pair at width 128, bitwise properties, memory discipline, the absence of an input range, argument errors, the host
+routes, two solver classes against the float64 oracle, and hipGraph capture.  Every test sets the switch "lem_wide_train" itself."""
 import copy
 import ctypes
+import os
+
+import numpy as np
 
 import pytest
 import torch
@@ -14,7 +17,7 @@ from helpers import synthetic_case, counted, tuned
 
 pytestmark = pytest.mark.gpu
 TW = 25
-WIDTHS = [33, 129, 164, 192, 256]       # one live channel in the last tile | one live column in the second 128-block | a pad inside a tile | exact tiles, ldg > Wp | the maximum
+WIDTHS = [33, 128, 129, 164, 192, 256]       # one live channel in the last tile | the flagship width: exact tiles, one 128-block | one live column in the second 128-block | a pad inside a tile | exact tiles, ldg > Wp | the maximum
 SHAPES = [(1, 1, 1), (5, 2, 33), (8, 25, 97), (4, 50, 64)]      # (ninp, T, n)
 
 
@@ -43,9 +46,9 @@ def _module(mp, ninp, width, seed, cls=None):
 
 
 def _apply(lem, xin, states=None):
-    from msmp_pde_amd.lem import _LEMWideTrainFunction
+    from msmp_pde_amd.lem import _LEMTrainFunction
     r = lem.rnn
-    return _LEMWideTrainFunction.apply(r, xin, r.weights, r.weights_lin_z, r.bias, r.bias_lin_z, *(states or (None, None)))
+    return _LEMTrainFunction.apply(r, xin, r.weights, r.weights_lin_z, r.bias, r.bias_lin_z, *(states or (None, None)))
 
 
 def _grads(lem):
@@ -106,25 +109,94 @@ def test_parity_with_the_float64_restatement(mp, width, ninp, t_len, n, with_sta
     _check_against_float64(lem, ref, xin, states, w_out, y, z, f'W={width} ninp={ninp} T={t_len} N={n} states={with_states}')
 
 
-@pytest.mark.parametrize('with_states', [False, True], ids=['zeros', 'states'])
-def test_width_128_agrees_with_the_128_wide_pair(mp, with_states):
-    """The new entries at width 128 against msmp_lem_train_fwd_f32 / _bwd_f32 (lem._LEMTrainFunction): same arithmetic, same bars."""
-    from msmp_pde_amd.lem import _LEMTrainFunction
-    lem, _ = _module(mp, 6, 128, 5)
-    n, t_len = 97, 25
-    xin = torch.randn(n, t_len, 6, device='cuda') * 0.7
+def test_width_128_reproduces_the_retired_128_wide_pair(mp):
+    """tests/golden/lem_train_128.npz was recorded on the parent of the commit that retired lem_train_kernel.hip, from ITS 128-wide pair
+    (msmp_lem_train_fwd_f32 / msmp_lem_train_bwd_f32 under LEMS(5, 128).forward_nodes with given initial states, T = 2, N = 33): y_T, z_T,
+    d bias, d bias_lin_z and rows 0 .. 7 of d weights and d weights_lin_z.  The surviving pair gives the same bits (torch.equal) through
+    the same call.  The parameters (270 KB), the states and dL/dy do not fit the fixture: they are regenerated from its seed by the host
+    generator, in the order of the recording, and each is pinned by its first row and its float64 sum; xin is stored whole."""
+    from msmp_pde_amd.lem import LEMS
+    d = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'lem_train_128.npz'))
+    ninp, t_len, n = (int(v) for v in d['shape'])
+    torch.manual_seed(int(d['seed']))
+    lems = LEMS(ninp, 128)
+    xin = torch.randn(n, t_len, ninp) * 0.7
+    y0, z0 = torch.rand(n, 128) * 2 - 1, torch.rand(n, 128) * 2 - 1
+    w_out = torch.randn(n, 128)
+    for k, v in list(lems.state_dict().items()) + [('y0', y0), ('z0', z0), ('w_out', w_out)]:
+        v = v.numpy()
+        total, recorded = v.astype(np.float64).sum(), float(d['sum.' + k])       # the sum to 1e-9: it may be reduced in another order
+        assert np.array_equal(v.reshape(v.shape[0], -1)[0], d['head.' + k]) and abs(total - recorded) <= 1e-9 * max(1.0, abs(recorded)), f'{k} is not what the fixture was recorded with'
+    assert np.array_equal(xin.numpy(), d['xin'])
+    lems = lems.cuda()
+    lems.states = (y0.cuda(), z0.cuda())
+    y = lems.forward_nodes(xin.cuda())
+    (y * w_out.cuda()).sum().backward()
+    g = {k: p.grad.cpu().numpy() for k, p in lems.named_parameters()}
+    got = {'y_T': y.detach().cpu().numpy(), 'z_T': lems.states[1].cpu().numpy(), 'd_bias': g['rnn.bias'], 'd_bias_lin_z': g['rnn.bias_lin_z'],
+           'd_weights_rows0_7': g['rnn.weights'][:8], 'd_weights_lin_z_rows0_7': g['rnn.weights_lin_z'][:8]}
+    for k, v in got.items():
+        assert torch.equal(torch.from_numpy(np.ascontiguousarray(v)), torch.from_numpy(d[k])), k
+
+
+def test_routes_at_width_128(mp, monkeypatch):
+    """lem.LEM._recurrence at the flagship width: LEM and LEMS under grad reach the forward (with `saved`) and the backward once each; LEM and
+    LEMS under no_grad, and LEM with frozen parameters, reach the forward with saved = NULL (the same bits) and never the backward; the
+    switch at 0 and TRAIN_KERNELS = False reach neither under grad and give the PyTorch restatement bit for bit."""
+    from msmp_pde_amd.lem import LEM, LEMS
+    L = mp.lib()
+    ninp, t_len, n = 5, 2, 33
+    lem, _ = _module(mp, ninp, 128, 81)
+    lems, _ = _module(mp, ninp, 128, 82, cls=LEMS)
+    xin = torch.randn(n, t_len, ninp, device='cuda') * 0.7
     w_out = torch.randn(n, 128, device='cuda')
-    states = (torch.rand(n, 128, device='cuda') * 2 - 1, torch.rand(n, 128, device='cuda') * 2 - 1) if with_states else (None, None)
-    r = lem.rnn
-    y0, z0 = _LEMTrainFunction.apply(lem, xin, r.weights, r.weights_lin_z, r.bias, r.bias_lin_z, *states)
-    (y0 * w_out).sum().backward()
-    g0 = _grads(lem)
-    lem.zero_grad(set_to_none=True)
-    y1, z1 = _apply(lem, xin, states)
-    (y1 * w_out).sum().backward()
-    assert (y1 - y0).abs().max().item() < 1e-5 and (z1 - z0).abs().max().item() < 1e-5
-    for a, b in zip(_grads(lem), g0):
-        assert (a - b).abs().max().item() < 1e-4 * b.abs().max().item()
+    real, saved_args = L.msmp_lem_train_fwd_wide_f32, []
+
+    def fwd(*a):          # (xin, n, t_len, ninp, width, dt, packed, y0, z0, saved, y_out, z_out, stream)
+        saved_args.append(a[9])
+        return real(*a)
+    monkeypatch.setattr(L, 'msmp_lem_train_fwd_wide_f32', fwd)
+    calls_b = counted(mp, monkeypatch, 'msmp_lem_train_bwd_wide_f32')
+
+    y = lem.forward_nodes(xin)
+    (y * w_out).sum().backward()
+    assert len(saved_args) == 1 and saved_args[0] is not None and len(calls_b) == 1
+    for k in range(2):
+        states = lems.states
+        yk = lems.forward_nodes(xin)
+        (yk * w_out).sum().backward()
+        assert (states is None) == (k == 0) and not lems.states[0].requires_grad
+    assert len(saved_args) == 3 and all(s is not None for s in saved_args) and len(calls_b) == 3
+
+    with torch.no_grad():
+        y_ng = lem.forward_nodes(xin)
+        lems.reset_states()
+        ys_ng = [lems.forward_nodes(xin) for _ in range(2)]
+    for p in lem.parameters():
+        p.requires_grad_(False)
+    y_frozen = lem.forward_nodes(xin)
+    for p in lem.parameters():
+        p.requires_grad_(True)
+    assert saved_args[3:] == [None] * 4 and len(calls_b) == 3
+    assert torch.equal(y_ng, y) and torch.equal(y_frozen, y) and not y_frozen.requires_grad
+    lems.reset_states()
+    assert torch.equal(lems.forward_nodes(xin), ys_ng[0]) and torch.equal(lems.forward_nodes(xin), ys_ng[1]) and not torch.equal(ys_ng[0], ys_ng[1])
+    n_f, n_b = len(saved_args), len(calls_b)
+
+    def restated(module, x):
+        return module.rnn(x.permute(1, 0, 2).contiguous())
+    with tuned(L, lem_wide_train=0):
+        y0 = lem.forward_nodes(xin)
+        assert y0.requires_grad and torch.equal(y0, restated(lem, xin))
+        (y0 * w_out).sum().backward()
+    monkeypatch.setattr(LEM, 'TRAIN_KERNELS', False)
+    y1 = lem.forward_nodes(xin)
+    assert y1.requires_grad and torch.equal(y1, restated(lem, xin))
+    lems.reset_states()
+    assert lems.forward_nodes(xin).requires_grad
+    monkeypatch.setattr(LEM, 'TRAIN_KERNELS', True)
+    assert len(saved_args) == n_f and len(calls_b) == n_b
+    assert (y0 - y).abs().max().item() < 1e-5
 
 
 def test_bitwise_properties(mp):

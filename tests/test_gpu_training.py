@@ -179,7 +179,7 @@ def test_training_step_runs_and_decreases_loss(mp):
 
 @pytest.mark.parametrize('ninp,n,t_len', [(3, 77, 25), (4, 300, 25), (6, 129, 50), (8, 40, 7), (1, 33, 3)])
 def test_lem_training_kernels_match_float64_restatement(mp, ninp, n, t_len):
-    """msmp_lem_train_fwd_f32 / msmp_lem_train_bwd_f32 (through LEM.forward_nodes) against the float64 PyTorch
+    """msmp_lem_train_fwd_wide_f32 / msmp_lem_train_bwd_wide_f32 at width 128 (through LEM.forward_nodes) against the float64 PyTorch
     restatement of the cell (LEMcuda.forward): final state and the gradients of the four parameters (the reference's
     LEMFunction returns exactly these, experiments/models_gnn.py:296-302).  fp32 vs float64: 1e-5 on the state
     (the north-star tolerance), 1e-4 of the largest entry on the gradients (sums over N*T rows in fp32)."""
