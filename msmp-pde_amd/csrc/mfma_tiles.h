@@ -81,6 +81,24 @@ __device__ __forceinline__ void acc_init_bias(const float* __restrict__ bias, in
         }
 }
 
+// The bias of a GEMM whose accumulators started at ZERO (node_update_kernel; acc_zero is below), added last.  A chain of
+// v_mfma_f32_32x32x2_f32 rounds its accumulator once per K = 2, each time relative to what the accumulator holds.  Started at the
+// bias, that is 64 (K = 128) to 128 roundings relative to |bias + sum|, and update_net_2's bias dominates its output for untrained
+// weights: the InstanceNorm behind it divides by the output's spread over the graph, far smaller than |y|.  Started at zero the
+// roundings are relative to the running sum alone and the bias costs one.
+template <int NB>
+__device__ __forceinline__ void acc_add_bias(const float* __restrict__ bias, int hh, f32x16 (&acc)[4][NB]) {
+#pragma unroll
+    for (int T = 0; T < 4; ++T)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const f32x4 bv = *reinterpret_cast<const f32x4*>(bias + 32 * T + 8 * q + 4 * hh);
+#pragma unroll
+            for (int m = 0; m < 4; ++m)
+#pragma unroll
+                for (int nb = 0; nb < NB; ++nb) acc[T][nb][4 * q + m] += bv[m];
+        }
+}
 
 // ------------------------------------------------------------------------------------------------
 // fp32 GEMM on the fp16 matrix pipe ("2-way fp16 split"), 5.3x fewer matrix-pipe cycles than

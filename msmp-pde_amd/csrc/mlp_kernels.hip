@@ -507,20 +507,11 @@ __global__ __launch_bounds__(256) void node_update_kernel(NodeArgs a) {
         nc[nb] = n[nb] < a.n_nodes ? n[nb] : a.n_nodes - 1;
     }
 
-    // acc init = b3 + W3[:, 256:256+nv] vars_n  (the variables columns of the concatenation, K = nv <= 8)
-    f32x16 z[4][NB];
-    acc_init_bias<NB>(a.b3, hh, z);
-    for (int v = 0; v < a.nv; ++v) {
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-            const float xv = a.vars[(size_t)nc[nb] * a.nv + v];
-#pragma unroll
-            for (int T = 0; T < 4; ++T)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    z[T][nb][r] = fmaf(a.w3v[(32 * T + acc_row(r, hh)) * MSMP_MAX_VARS + v], xv, z[T][nb][r]);
-        }
-    }
+    // Both GEMMs: accumulators from zero, each half of K summed on its own (update_net_1: the h columns, then the agg columns), bias
+    // last (mfma_tiles.h, acc_add_bias): with the bias first and one accumulator the gated classes at depth 6 were 3 - 6.6 x farther
+    // from the reference than a float32 evaluation of the same formulas (tests/test_gpu_reference_golden.py).
+    f32x16 z[4][NB], first[4][NB];
+    acc_zero<NB>(z);
 
     WStage ws;
     f32x4 bcur[NB][4], bnext[NB][4];
@@ -547,6 +538,13 @@ __global__ __launch_bounds__(256) void node_update_kernel(NodeArgs a) {
                 for (int q = 0; q < 4; ++q) bnext[nb][q] = *reinterpret_cast<const f32x4*>(p + 8 * q);
             }
         }
+        if (ch == 4) {
+#pragma unroll
+            for (int T = 0; T < 4; ++T)
+#pragma unroll
+                for (int nb = 0; nb < NB; ++nb) first[T][nb] = z[T][nb];
+            acc_zero<NB>(z);
+        }
         mma_chunk<NB>(lds + (ch & 1) * H * LDW, c, hh, bcur, z);
         wstage_store(ws, lds + ((ch + 1) & 1) * H * LDW, tid);
         __syncthreads();
@@ -554,6 +552,24 @@ __global__ __launch_bounds__(256) void node_update_kernel(NodeArgs a) {
         for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
             for (int q = 0; q < 4; ++q) bcur[nb][q] = bnext[nb][q];
+    }
+
+    // + b3 + W3[:, 256:256+nv] vars_n  (the variables columns of the concatenation, K = nv <= 8)
+#pragma unroll
+    for (int T = 0; T < 4; ++T)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) z[T][nb] += first[T][nb];
+    acc_add_bias<NB>(a.b3, hh, z);
+    for (int v = 0; v < a.nv; ++v) {
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) {
+            const float xv = a.vars[(size_t)nc[nb] * a.nv + v];
+#pragma unroll
+            for (int T = 0; T < 4; ++T)
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    z[T][nb][r] = fmaf(a.w3v[(32 * T + acc_row(r, hh)) * MSMP_MAX_VARS + v], xv, z[T][nb][r]);
+        }
     }
 
 #pragma unroll
@@ -564,16 +580,28 @@ __global__ __launch_bounds__(256) void node_update_kernel(NodeArgs a) {
             for (int r = 0; r < 16; ++r) z[T][nb][r] = swishf(z[T][nb][r]);
 
     f32x16 y[4][NB];
-    acc_init_bias<NB>(a.b4, hh, y);
+    acc_zero<NB>(y);
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         if (t < 3) wstage_load(ws, a.w4 + (size_t)(t + 1) * CHUNK_FLOATS, tid);
+        if (t == 2) {
+#pragma unroll
+            for (int T = 0; T < 4; ++T)
+#pragma unroll
+                for (int nb = 0; nb < NB; ++nb) first[T][nb] = y[T][nb];
+            acc_zero<NB>(y);
+        }
         mma_chunk_from_acc<NB>(lds + (t & 1) * H * LDW, c, hh, z[t], y);
         if (t < 3) {
             wstage_store(ws, lds + ((t + 1) & 1) * H * LDW, tid);
             __syncthreads();
         }
     }
+#pragma unroll
+    for (int T = 0; T < 4; ++T)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) y[T][nb] += first[T][nb];
+    acc_add_bias<NB>(a.b4, hh, y);
 
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {

@@ -701,8 +701,10 @@ class _GLUBase(_SolverBase):
         del self.output_mlp
         mk = lambda: nn.Sequential(_Conv1dNoMIOpen(comps, 8, 6, stride=2, dtype=torch.float32), Swish(),
                                    _Conv1dNoMIOpen(8, comps, 15, stride=1, dtype=torch.float32))
-        self.output_mlp_gate = mk()
-        self.output_mlp_diff = mk()
+        # registration order = order of state_dict() and parameters(), which an optimizer.state_dict() is indexed by: the 1-D reference
+        # class registers gate, then diff (models_gnn.py), the 2-D one diff, then gate (models_gnn2D.py:1291-1295)
+        for name in (('output_mlp_diff', 'output_mlp_gate') if self.TWO_D else ('output_mlp_gate', 'output_mlp_diff')):
+            setattr(self, name, mk())
 
     def _decode_hip(self, h, u, tw):
         """The decoder as one HIP launch (2-D: behind double_mlp as one row GEMM), or None where the PyTorch ops below apply: under

@@ -10,10 +10,16 @@ Pinning status (see DESIGN.md "Oracle"):
     /root/reference/experiments/models_gnn.py, models_gnn2D.py and common/utils.py unchanged (on
     pure-torch stand-ins for the third-party packages this image lacks) and stores inputs/outputs in
     tests/golden/*.npz; tests/test_oracle_golden.py checks every function below against them.
+    That holds for all seventeen solver classes: the LEM, LSTM, GLU, G2, MSSMP and state-saving ones run there on
+    a functional stand-in for `lem_cuda` (`gen_golden.py recurrent`), which pins everything the reference computes
+    around the LEM cell: input assembly and column order, the LEMcuda parameter layout, dt = 1, lemoutput_mlp,
+    gating, the G2 blend, the GLU halves, the MSSMP composition and the LEMS state carry.  The LSTM classes run
+    torch.nn.LSTM and are pinned completely.
   * UNPINNED: the third-party primitives themselves (PyG propagate/mean, PyG InstanceNorm,
-    torch_cluster radius_graph/knn_graph) and the LEM recurrence (`lem_cuda`, source absent from the
-    reference tree).  The reference holds no fixture for them; they follow the published behaviour
-    of those packages.
+    torch_cluster radius_graph/knn_graph) and the cell arithmetic of the LEM recurrence (`lem_cuda`, source
+    absent from the reference tree; the stand-in and `lem_forward` below both state the published cell).  The
+    reference holds no fixture for them; they follow the published behaviour of those packages (SURVEY.md
+    section 8c).
 
 Every function cites the reference file:line it follows (paths relative to /root/reference).
 All arrays are row-major numpy; `edge_index` is int64 [2, E] with row 0 = source j, row 1 = target i.
@@ -132,7 +138,8 @@ def lem_forward(inputs, weights, weights_lin_z, bias, bias_lin_z, dt=1.0, states
       z <- (1-dt_) z + dt_ tanh(g3); X2 = [z, x_t]; y <- (1-dt_bar) y + dt_bar tanh(X2 Wz^T + bz).
     inputs [T, N, ninp]; returns all_y[-1] (LEM.forward, :340-342).  `states` = (y0, z0) as LEMcuda.forward takes them
     (:325-332; the stateful LEMS carries (all_y[-1], all_z[-1]) from call to call, :345-357); return_state adds all_z[-1].
-    PARITY UNPINNED."""
+    The cell arithmetic is UNPINNED; the call (argument order, parameter layout, dt, state carry, which output the classes take)
+    is pinned through the reference's own classes, tests/test_oracle_golden.py::test_recurrent_classes_vs_reference."""
     t_len, n, _ = inputs.shape
     nh = weights_lin_z.shape[0]
     y = np.zeros((n, nh), dtype=inputs.dtype) if states is None else np.asarray(states[0], dtype=inputs.dtype)

@@ -44,7 +44,7 @@ def mp_layer(sd, prefix, x, u, pos, variables, ei, batch, b, lin):
 
 
 def lem_forward(inputs, w, wz, bias, bz, dt=1.0, states=None):
-    """See msmp_oracle.lem_forward (PARITY UNPINNED)."""
+    """See msmp_oracle.lem_forward (only the cell arithmetic is unpinned)."""
     t_len, n, _ = inputs.shape
     nh = wz.shape[0]
     y, z = (torch.zeros(n, nh, dtype=inputs.dtype, device=inputs.device), torch.zeros(n, nh, dtype=inputs.dtype, device=inputs.device)) if states is None else states

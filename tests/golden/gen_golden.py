@@ -23,9 +23,16 @@ Fixtures written:
                                  LEM-free classes; the 0.6-1.3 M parameters are not stored but re-created from
                                  seeded_weights.seeded_state_dict (same function in the tests), so a fixture is ~100 KB
 
-    python tests/golden/gen_golden.py            # everything
-    python tests/golden/gen_golden.py deep       # only the full-depth fixtures
+  deep_{class}_{experiment}[_tw{tw}][_save].npz   the same for the LEM, LSTM, GLU, G2, MSSMP and state-saving classes (and for
+                                 time windows 20 and 50), two graphs each: mode `recurrent`.  The reference's LEM calls the absent
+                                 lem_cuda extension; standins/lem_cuda is our own torch statement of the published cell, so these
+                                 fixtures pin everything the reference computes AROUND the cell (standins/README.md)
+
+    python tests/golden/gen_golden.py            # everything but the recurrent fixtures (those keep a generator of their own)
+    python tests/golden/gen_golden.py deep       # only the full-depth fixtures of the LEM-free classes
+    python tests/golden/gen_golden.py recurrent  # only the recurrent / GLU / time-window fixtures; rewrites no other file
 """
+import contextlib
 import os
 import sys
 
@@ -88,8 +95,10 @@ def sine_traj(rng, b, nt, x, tmax, length):
     return out
 
 
-def make_case(name, rng, bsz):
-    """(pde, creator, u_super, x, variables, eq_variables) for the four in-scope experiment shapes."""
+def make_case(name, rng, bsz, tw=None):
+    """(pde, creator, u_super, x, variables, eq_variables) for the four in-scope experiment shapes; `tw`: the GraphCreator's time
+    window (default: the module's TW)."""
+    tw = TW if tw is None else tw
     if name == 'E2':
         pde = CE(device='cpu')
         pde.tmin, pde.tmax, pde.grid_size = 0.0, 4.0, [NT, NX]
@@ -125,7 +134,7 @@ def make_case(name, rng, bsz):
         eqv = {'a': 1., 'b': 1.}
     else:
         raise ValueError(name)
-    creator = U.GraphCreator(pde=pde, neighbors=3, time_window=TW, t_resolution=NT, x_resolution=NX)
+    creator = U.GraphCreator(pde=pde, neighbors=3, time_window=tw, t_resolution=NT, x_resolution=NX)
     x = f32r(x)
     return pde, creator, f32r(u), x, variables, eqv
 
@@ -294,10 +303,102 @@ def gen_deep():
         save(os.path.join(HERE, f'deep_{name}_{exp}.npz'), d)
         print('deep', name, exp, 'params', sum(p.numel() for p in model.parameters()), 'out max', float(pred.abs().max()))
 
+# (class, experiment, time window, unrolled steps, save_state constructor argument).  tests/helpers.py RECURRENT_CASES names the
+# same fixtures; the weights seed of a case is 8000 + its index here unless RECURRENT_SEEDS names another.
+RECURRENT_CASES = [
+    ('MP_PDE_SolverLEMLin', 'E2', 25, 1, None),
+    ('MP_PDE_SolverLEMLinGated', 'E2', 25, 1, None), ('MP_PDE_SolverLEMLinGated', 'WE3', 25, 1, None),
+    ('MP_PDE_SolverLEMLinGatedGLU', 'E2', 25, 1, None), ('MP_PDE_SolverLEMLinGatedGLU', 'WE3', 25, 1, None),
+    ('MP_PDE_SolverLSTMLin', 'WE3', 25, 1, None), ('MP_PDE_SolverLSTMLinGated', 'E2', 25, 1, None),
+    ('MSSMP_PDE_Solver', 'E2', 25, 1, None),
+    ('MP_PDE_SolverLEMLinGatedSave', 'E2', 25, 2, None),
+    ('MP_PDE_Solver2DLEMLinGated', 'RPU', 25, 2, True),
+    ('MP_PDE_Solver2DLEMLin', 'MSWG3', 25, 1, None),
+    ('MP_PDE_Solver2DLEMLinGated', 'MSWG3', 25, 1, None), ('MP_PDE_Solver2DLEMLinGated', 'RPU', 25, 1, None),
+    ('MP_PDE_Solver2DLEMLinG2', 'RPU', 25, 1, None),
+    ('MP_PDE_Solver2DLSTMLin', 'MSWG3', 25, 1, None), ('MP_PDE_Solver2DLSTMLinGated', 'RPU', 25, 1, None),
+    ('MP_PDE_Solver2DLEMLinGatedGLU', 'MSWG3', 25, 1, None), ('MP_PDE_Solver2DLEMLinGatedGLU', 'RPU', 25, 1, None),
+    ('MP_PDE_Solver', 'E2', 20, 1, None), ('MP_PDE_Solver', 'E2', 50, 1, None),
+    ('MP_PDE_SolverLEMLinGated', 'E2', 20, 1, None), ('MP_PDE_SolverLEMLinGated', 'E2', 50, 1, None),
+    ('MP_PDE_Solver2DLEMLinGated', 'MSWG3', 50, 1, None),
+]
+
+# The GPU tests hold the HIP path to max(1e-5, 2 x the float32 floor of the oracle) and require the forward's numpy float32 floor to be
+# <= 1e-4 max(1, |ref|), so that the floor cannot hide a failure.  The untrained 1-D gated stacks on WE3 are the worst conditioned:
+# with seed 8000 + index their floors were 1.2e-4 (LEMLinGated/WE3), 6.2e-5 (GLU/E2) and 8.0e-5 (GLU/WE3); with the seeds below
+# 4.0e-5, 2.1e-5 and 5.6e-5 (measured on the CPU with the float32 numpy oracle when these fixtures were generated).
+RECURRENT_SEEDS = {2: 8102, 3: 8403, 4: 8404}
+
+
+def recurrent_fixture_name(name, exp, tw, save):
+    return f'deep_{name}_{exp}' + (f'_tw{tw}' if tw != 25 else '') + ('_save' if save else '') + '.npz'
+
+
+@contextlib.contextmanager
+def cuda_is_identity():
+    """LEMcuda.__init__ moves its dt to the GPU (experiments/models_gnn.py:314); the build container has none.  For the body of the
+    `with`, torch.Tensor.cuda returns the tensor itself; the method is put back afterwards."""
+    real = torch.Tensor.cuda
+    torch.Tensor.cuda = lambda self, *a, **k: self
+    try:
+        yield
+    finally:
+        torch.Tensor.cuda = real
+
+
+def gen_recurrent():
+    """Full-depth fixtures of the classes gen_deep leaves out (LEM, LSTM, GLU, G2, MSSMP, the state-saving ones) and of the time
+    windows 20 and 50: the reference's classes at hidden_layer = 6 with seeded parameters on two graphs, forward + unrolled steps.
+    The state-saving classes keep their LEM states over the unrolled steps, as the reference's rollout does."""
+    sys.path.insert(0, HERE)
+    from seeded_weights import seeded_state_dict
+    rng = np.random.default_rng(20261020)      # a generator of its own: no other fixture depends on its draws
+    bsz = 2
+    for idx, (name, exp, tw, n_roll, save_arg) in enumerate(RECURRENT_CASES):
+        cls = getattr(M2 if '2D' in name else M, name)
+        pde, creator, u, x, variables, eqv = make_case(exp, rng, bsz, tw)
+        kw = {} if save_arg is None else {'save_state': save_arg}
+        seed = RECURRENT_SEEDS.get(idx, 8000 + idx)
+        first = 2 * tw
+        steps = [first] * bsz
+        with cuda_is_identity():
+            model = cls(pde, time_window=tw, eq_variables=eqv, hidden_layer=6, **kw)
+            shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
+            sd = seeded_state_dict(shapes, seed)
+            model.load_state_dict({k: torch.tensor(v.astype(np.float64)) for k, v in sd.items()}, strict=True)
+            model.eval()
+            g, ut = build_graph(creator, u, x, variables, steps)
+            d = {'experiment': exp, 'hidden_layer': 6, 'weights_seed': seed, 'time_window': tw, 'first_step': first,
+                 'save_state': bool(save_arg) or name.endswith('Save'),
+                 'u_super': u[:, :first + tw * (n_roll + 2)], 'x_grid': x,
+                 'tmin': pde.tmin, 'tmax': pde.tmax, 'dt': pde.dt, 'L': float(pde.L), 'steps': np.array(steps),
+                 'param_names': np.array(list(shapes.keys())), 'param_shapes': np.array([','.join(str(n) for n in s) for s in shapes.values()]),
+                 'param_checksum': np.float64(sum(float(np.abs(v.astype(np.float64)).sum()) for v in sd.values()))}
+            d.update({'var_' + k: v for k, v in variables.items()})
+            d.update(graph_to_np(g, 'g_'))
+            with torch.no_grad():
+                pred = model(g)
+                d['out'] = pred.numpy().copy()
+                step = first
+                for r in range(n_roll):     # experiments/train_helper.py:255-261
+                    step += tw
+                    same = [step] * bsz
+                    _, labels = creator.create_data(ut, same)
+                    g = creator.create_next_graph(g, pred, labels, same)
+                    pred = model(g)
+                    d[f'roll{r}'] = pred.numpy().copy()
+        d['n_roll'] = n_roll
+        path = os.path.join(HERE, recurrent_fixture_name(name, exp, tw, save_arg))
+        save(path, d)
+        print('recurrent', os.path.basename(path), 'params', sum(p.numel() for p in model.parameters()),
+              'out max %.3g' % float(pred.abs().max()), 'KB', os.path.getsize(path) // 1024)
+
 
 if __name__ == '__main__':
     if len(sys.argv) > 1 and sys.argv[1] == 'deep':
         gen_deep()
+    elif len(sys.argv) > 1 and sys.argv[1] == 'recurrent':
+        gen_recurrent()
     else:
         rng = np.random.default_rng(20261004)
         gen_graphs(rng)

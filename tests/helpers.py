@@ -59,6 +59,72 @@ def deep_state_dict(d, shapes=None):
 DEEP_CASES = [('MP_PDE_Solver', 'E2'), ('MP_PDE_SolverGated', 'E2'), ('MP_PDE_SolverGated', 'WE3'),
               ('MP_PDE_Solver2DGated', 'MSWG3'), ('MP_PDE_Solver2DGated', 'RPU')]
 
+# The fixtures of `gen_golden.py recurrent`: (class, experiment, time window, save_state constructor argument) of the reference's
+# LEM, LSTM, GLU, G2, MSSMP and state-saving classes at depth 6 on two graphs, and of the time windows 20 and 50.  Their LEM ran
+# tests/golden/standins/lem_cuda (the published cell; the extension itself is absent), everything around it is the reference's own code.
+RECURRENT_CASES = [
+    ('MP_PDE_SolverLEMLin', 'E2', 25, None),
+    ('MP_PDE_SolverLEMLinGated', 'E2', 25, None), ('MP_PDE_SolverLEMLinGated', 'WE3', 25, None),
+    ('MP_PDE_SolverLEMLinGatedGLU', 'E2', 25, None), ('MP_PDE_SolverLEMLinGatedGLU', 'WE3', 25, None),
+    ('MP_PDE_SolverLSTMLin', 'WE3', 25, None), ('MP_PDE_SolverLSTMLinGated', 'E2', 25, None),
+    ('MSSMP_PDE_Solver', 'E2', 25, None),
+    ('MP_PDE_SolverLEMLinGatedSave', 'E2', 25, None),
+    ('MP_PDE_Solver2DLEMLinGated', 'RPU', 25, True),
+    ('MP_PDE_Solver2DLEMLin', 'MSWG3', 25, None),
+    ('MP_PDE_Solver2DLEMLinGated', 'MSWG3', 25, None), ('MP_PDE_Solver2DLEMLinGated', 'RPU', 25, None),
+    ('MP_PDE_Solver2DLEMLinG2', 'RPU', 25, None),
+    ('MP_PDE_Solver2DLSTMLin', 'MSWG3', 25, None), ('MP_PDE_Solver2DLSTMLinGated', 'RPU', 25, None),
+    ('MP_PDE_Solver2DLEMLinGatedGLU', 'MSWG3', 25, None), ('MP_PDE_Solver2DLEMLinGatedGLU', 'RPU', 25, None),
+    ('MP_PDE_Solver', 'E2', 20, None), ('MP_PDE_Solver', 'E2', 50, None),
+    ('MP_PDE_SolverLEMLinGated', 'E2', 20, None), ('MP_PDE_SolverLEMLinGated', 'E2', 50, None),
+    ('MP_PDE_Solver2DLEMLinGated', 'MSWG3', 50, None),
+]
+
+
+def recurrent_id(case):
+    kind, exp, tw, save = case
+    return f'{kind}/{exp}' + (f'/tw{tw}' if tw != 25 else '') + ('/save' if save else '')
+
+
+def load_recurrent(case):
+    """The fixture of one RECURRENT_CASES row; what the row says is what the fixture recorded."""
+    kind, exp, tw, save = case
+    d = load(f'deep_{kind}_{exp}' + (f'_tw{tw}' if tw != 25 else '') + ('_save' if save else '') + '.npz')
+    assert str(d['experiment']) == exp and int(d['time_window']) == tw and int(d['first_step']) == 2 * tw and int(d['hidden_layer']) == 6
+    assert bool(d['save_state']) == (bool(save) or kind.endswith('Save'))
+    assert d['u_super'].shape[1] == 2 * tw + tw * (int(d['n_roll']) + 2)
+    return d
+
+
+def recurrent_oracle_rollout(case, d, sd, dtype=np.float64, torch_edition=False):
+    """[forward, unrolled step 1, ...] of the oracle on one RECURRENT_CASES fixture, every step on the graph made from the oracle's
+    own previous prediction (experiments/train_helper.py:255-261).  The state-saving fixtures carry the LEM states from step to
+    step.  torch_edition: oracle/msmp_oracle_torch.py (float64); it takes initial LEM states but returns none, so there the numpy
+    oracle advances the states on the same graphs."""
+    from oracle import msmp_oracle as O, msmp_oracle_torch as OT
+    kind, exp, tw, _ = case
+    pde_name, eqv, _ = EXPERIMENTS[exp]
+    pde, g = pde_of(d), graph_of(d)
+    states = {} if bool(d['save_state']) else None
+    u = d['u_super'].astype(np.float64)
+    same = lambda step: [step] * len(u)
+
+    def forward(g):
+        if not torch_edition:
+            return O.solver_forward(kind, sd, g, pde, tw, eqv, 6, dtype=dtype, lem_states=states)
+        out = OT.solver_forward(kind, sd, g, pde, tw, eqv, 6, lem_initial_states=None if states is None else states.get('states'))
+        if states is not None:
+            O.solver_forward(kind, sd, g, pde, tw, eqv, 6, lem_states=states)
+        return out
+    preds, step = [forward(g)], int(d['first_step'])
+    for _ in range(int(d['n_roll'])):
+        step += tw
+        _, labels = O.create_data(u, same(step), tw)
+        g = O.create_next_graph(pde_name, pde, tw, g, preds[-1], labels, same(step))
+        preds.append(forward(g))
+    return preds
+
+
 _PARITY_LOG = os.environ.get('MSMP_PARITY_LOG', os.path.join(os.path.dirname(GOLDEN), '..', 'gpurun_out', 'parity_r04.json'))
 
 

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import load, sd_of, graph_of, EXPERIMENTS, synthetic_case
+from helpers import load, sd_of, graph_of, EXPERIMENTS, synthetic_case, DEEP_CASES, RECURRENT_CASES, recurrent_id, load_recurrent, deep_shapes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -192,11 +192,52 @@ def test_state_dict_is_reference_compatible(mp, kind):
     assert repr(model) == 'GNN' and model.eq_variables == eqv
 
 
+def _layout_cases():
+    """(id, class, experiment, time window, constructor arguments, fixture loader, depth) of every fixture that records a reference
+    class's state_dict: the four solver_* (the order of their sd_* keys), the deep_* and the `gen_golden.py recurrent` ones."""
+    cases = [(f'solver/{kind}', kind, None, 25, {}, (lambda kind=kind: load(f'solver_{kind}.npz')))
+             for kind in ('MP_PDE_Solver', 'MP_PDE_SolverGated', 'MP_PDE_Solver2D', 'MP_PDE_Solver2DGated')]
+    cases += [(f'deep/{kind}/{exp}', kind, exp, 25, {}, (lambda kind=kind, exp=exp: load(f'deep_{kind}_{exp}.npz'))) for kind, exp in DEEP_CASES]
+    cases += [(recurrent_id(c), c[0], c[1], c[2], {} if c[3] is None else {'save_state': c[3]}, (lambda c=c: load_recurrent(c))) for c in RECURRENT_CASES]
+    return cases
+
+
+def test_layout_cases_cover_all_seventeen_classes():
+    from oracle import msmp_oracle as O
+    assert len(O.KINDS_1D + O.KINDS_2D) == 17 and {c[1] for c in _layout_cases()} == set(O.KINDS_1D + O.KINDS_2D)
+
+
+@pytest.mark.parametrize('case', _layout_cases(), ids=lambda c: c[0])
+def test_state_dict_layout_is_the_references(mp, case):
+    """For every one of the seventeen classes (and the time windows 20 and 50, and save_state=True): state_dict() of the drop-in
+    class has the names the REFERENCE's class has, in its order, with its shapes, as the generator recorded them from the
+    reference's own class.  The order matters beyond load_state_dict: parameters() follows it, and an optimizer.state_dict() is
+    indexed by position, so two equally shaped modules in swapped order (the two GLU decoders) would exchange their moments
+    without an error.  All tensors are float32 and a float64 checkpoint loads."""
+    _, kind, exp, tw, kw, fixture = case
+    d = fixture()
+    exp = str(d['experiment']) if exp is None else exp
+    if 'param_names' in d:
+        want = deep_shapes(d)
+    else:
+        want = {k[3:]: v.shape for k, v in d.items() if k.startswith('sd_')}       # npz keeps the order the generator stored
+    pde_name, eqv, unstructured = EXPERIMENTS[exp]
+    pde = {'CE': mp.CE, 'WE': mp.WE, 'AD': mp.AD}[pde_name]()
+    model = getattr(mp, kind)(pde, time_window=tw, eq_variables=eqv, hidden_layer=int(d['hidden_layer']), **kw)
+    sd = model.state_dict()
+    assert list(sd) == list(want)
+    assert [tuple(v.shape) for v in sd.values()] == [tuple(s) for s in want.values()]
+    assert [n for n, _ in model.named_parameters()] == list(want)        # no buffers: parameters() has the same order
+    assert all(v.dtype == torch.float32 for v in sd.values())
+    model.load_state_dict({k: torch.zeros(s, dtype=torch.float64) for k, s in want.items()}, strict=True)
+    assert all(v.dtype == torch.float32 for v in model.state_dict().values())
+
+
 @pytest.mark.parametrize('kind,comps', [('MP_PDE_SolverLEMLinGatedGLU', 1), ('MP_PDE_Solver2DLEMLinGatedGLU', 2)])
 def test_glu_classes_have_the_reference_layout(mp, kind, comps):
-    """The GLU classes cannot be instantiated from the reference here (their LEM needs the absent lem_cuda), so the
-    state_dict layout is checked against the constructor arithmetic of experiments/models_gnn.py:1379-1462 /
-    models_gnn2D.py:1198-1296: hidden width 164, GNN_LayerLin with time_window = comps * 25, LEM(2 + len(eq_variables) + comps, 164),
+    """The state_dict layout of the GLU classes against the constructor arithmetic of experiments/models_gnn.py:1379-1462 /
+    models_gnn2D.py:1198-1296 (names and shapes, not the order; test_state_dict_layout_is_the_references holds them to the
+    reference's own classes, which do run on the build machine with a stand-in for the absent lem_cuda): hidden width 164, GNN_LayerLin with time_window = comps * 25, LEM(2 + len(eq_variables) + comps, 164),
     two decoders Conv1d(comps, 8, 6, stride 2) -> Conv1d(8, comps, 15)."""
     eqv = {'beta': 0.2} if comps == 1 else {'a': 1.0, 'b': 1.0}
     nv, W, tw = len(eqv) + 1, 164, 25 * comps

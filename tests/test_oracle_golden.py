@@ -4,7 +4,8 @@ import numpy as np
 import pytest
 
 from oracle import msmp_oracle as O
-from helpers import load, sd_of, graph_of, pde_of, EXPERIMENTS, DEEP_CASES, deep_state_dict
+from helpers import (load, sd_of, graph_of, pde_of, EXPERIMENTS, DEEP_CASES, deep_state_dict, RECURRENT_CASES, recurrent_id, load_recurrent,
+                     recurrent_oracle_rollout)
 
 TW = 25
 TOL = 1e-12
@@ -91,7 +92,8 @@ def test_torch_oracle_matches_golden(kind):
 
 
 def test_torch_oracle_matches_numpy_oracle_lem():
-    """LEM solvers have no golden vector (lem_cuda absent): the two oracle editions must at least agree."""
+    """The two oracle editions agree on LEM solvers with default-initialised weights at depth 2 (the reference's classes pin both
+    editions around the cell in test_recurrent_classes_vs_reference; only the cell arithmetic of the absent lem_cuda is unpinned)."""
     from oracle import msmp_oracle_torch as OT
     import torch
     import msmp_pde_amd as mp
@@ -119,7 +121,8 @@ def test_float32_noise_floor_recorded():
 
 
 def test_lem_cell_properties():
-    """LEM recurrence (PARITY UNPINNED: lem_cuda source is absent).  Property checks only: with dt=0
+    """LEM cell arithmetic (the one part of the LEM path still UNPINNED: lem_cuda's source is absent, and the fixtures of
+    `gen_golden.py recurrent` ran our stand-in of the published cell).  Property checks only: with dt=0
     the state stays zero; output is bounded by 1 (convex combination of tanh values)."""
     rng = np.random.default_rng(0)
     nh, ninp, n, t = 16, 4, 7, 5
@@ -149,3 +152,35 @@ def test_full_depth_solver_vs_reference(kind, exp):
         preds = O.rollout(kind, sd, g, pde_name, pde, TW, eqv, 6, u, 50, n_roll)
         for r in range(n_roll):
             assert np.abs(preds[r + 1] - d[f'roll{r}']).max() < 1e-8 * max(1.0, np.abs(d[f'roll{r}']).max()), r
+
+
+@pytest.mark.parametrize('edition', ['numpy', 'torch'])
+@pytest.mark.parametrize('case', RECURRENT_CASES, ids=recurrent_id)
+def test_recurrent_classes_vs_reference(case, edition):
+    """The LEM, LSTM, GLU, G2, MSSMP and state-saving classes, and the time windows 20 and 50, at full depth: both editions of the
+    oracle against the output of the REFERENCE's class with the same seeded parameters (`gen_golden.py recurrent`), forward and
+    every unrolled step; bars of test_full_depth_solver_vs_reference.  The reference's LEM ran the stand-in of the absent lem_cuda
+    (the published cell: that arithmetic alone stays unpinned); input assembly and column order, the LEMcuda parameter layout,
+    dt = 1, lemoutput_mlp, gating, the G2 blend, the GLU halves, the MSSMP composition and the LEMS state carry are the
+    reference's own code.  State-saving fixtures: the states are carried over both unrolled steps, the carry changes the first
+    unrolled step by more than 100 x its bar, and a fresh state dict on the first graph gives `out` again."""
+    kind, exp, tw, _ = case
+    d = load_recurrent(case)
+    sd = {k: v.astype(np.float64) for k, v in deep_state_dict(d).items()}
+    preds = recurrent_oracle_rollout(case, d, sd, torch_edition=edition == 'torch')
+    n_roll = int(d['n_roll'])
+    assert len(preds) == n_roll + 1 and preds[0].shape == d['out'].shape
+    rel = lambda a, ref: np.abs(a - ref).max() / max(1.0, np.abs(ref).max())
+    err = rel(preds[0], d['out'])
+    assert err < 1e-9, err
+    for r in range(n_roll):
+        assert rel(preds[r + 1], d[f'roll{r}']) < 1e-8, r
+    if bool(d['save_state']):
+        assert n_roll == 2
+        _, eqv, _ = EXPERIMENTS[exp]
+        fresh = {}
+        again = O.solver_forward(kind, sd, graph_of(d), pde_of(d), tw, eqv, 6, lem_states=fresh)
+        assert rel(again, d['out']) < 1e-9 and 'states' in fresh
+        d_stateless = dict(d, save_state=np.bool_(False))
+        no_carry = recurrent_oracle_rollout(case, d_stateless, sd)
+        assert rel(no_carry[1], d['roll0']) > 100 * 1e-8, 'the fixture does not see the state carry'      # a lost carry misses the bar of the unrolled steps by two orders of magnitude at least
