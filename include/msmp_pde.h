@@ -52,12 +52,12 @@ extern "C" {
 
 typedef void* msmp_stream_t;
 
-/* ABI version: 420 = the five entries of the 128-wide LEM training pair removed (msmp_lem_train_fwd_wide_f32 / _bwd_wide_f32 serve every
+/* ABI version: 430 = the six msmp_*mlp_train* entries and the switch "mlp_train" added; 420 = the five entries of the 128-wide LEM training pair removed (msmp_lem_train_fwd_wide_f32 / _bwd_wide_f32 serve every
  * width) and the blob of msmp_pack_lem_f32 without its last section, which only that pair read; 410 = msmp_mp_layer_decode_f32 and msmp_decoder_t removed;
  * 400 = round 4 (msmp_tiles_t: listed, period_tiles, period_nodes; msmp_build_tiles writes 3 statistics);
  * 300 = round 3 (msmp_last_status, msmp_tiles_t checked on every entry point that takes one).  Bumped whenever a
  * prototype or a blob layout changes; the ctypes host refuses a library whose version is not the one it was written for. */
-#define MSMP_ABI_VERSION 420
+#define MSMP_ABI_VERSION 430
 int msmp_version(void);
 const char* msmp_last_error(void);
 
@@ -123,6 +123,11 @@ int msmp_last_status(int* flags_out, int reset);
  *             themselves do not read the key; any value other than 0 selects the kernels).  The GLU classes take them only while "wide_msg",
  *             "split" and "lem_wide" are 1 as well.  CPU tensors, float64, a `u` that requires grad and sizes the entries refuse by value
  *             keep the PyTorch ops.  Measured: DESIGN.md section 4.24.
+ *   "mlp_train" 1 (default): under autograd the host's Swish MLPs around the encoder and decoder (embedding_mlp, lemoutput_mlp,
+ *             lstmoutput_mlp, double_mlp) are one msmp_mlp_train_fwd_f32 launch forward and one msmp_mlp_train_bwd_f32 call backward;
+ *             0: the PyTorch module (library GEMMs and elementwise kernels) differentiated by torch.autograd (the entries themselves
+ *             do not read the key; any value other than 0 selects the kernels).  CPU tensors, float64, a call in which nothing requires
+ *             grad and sizes the entries refuse by value keep the PyTorch ops.  Measured: DESIGN.md section 4.25.
  *   "tile_arith" 1 (default): ranged tiles take their node rows by arithmetic on tile_halo; 0: always through the node list.
  *   "tile_align" 0 (default): the host cuts the node tiles of a batch of identical graphs at graph boundaries only where tile_nodes divides
  *             the graph size; 1: also where it does not (bitwise graph-order / sharding equivariance on knn graphs, 11-20 % more tiles
@@ -618,6 +623,40 @@ int msmp_lem_train_fwd_wide_f32(const float* xin, int64_t n_nodes, int t_len, in
  * reference's use of it, no gradient of the step inputs is produced (:300-302), nor of the initial states (carried constants, :350-353). */
 int msmp_lem_train_bwd_wide_f32(const float* grad_y, const float* saved, const float* y0, const float* z0, int64_t n_nodes, int t_len,
                                 int width, float dt, const float* packed_bwd, float* dg_out, msmp_stream_t stream);
+/* The Swish MLPs around the encoder and decoder for TRAINING (mlp_train_kernel.hip): forward with the pre-activations saved and the whole
+ * backward, one kernel launch each, in the fp32-exact three-way bf16 split of the pair above (no input range; the range status is neither
+ * read nor raised).  Parameters in nn.Linear's layout (experiments/models_gnn.py: embedding_mlp, lemoutput_mlp, double_mlp):
+ *   layers 2, heads 1:       out = Swish(w2 Swish(w1 x + b1) + b2)      w1 [width, k_in], b1 [width], w2 [width, width], b2 [width]
+ *   layers 1, heads 1 | 2:   out = Swish(w1 x + b1)                     w1 [heads width, k_in], b1 [heads width]; w2, b2 unused (NULL)
+ * with 1 <= k_in <= 256 and 1 <= width <= 256: head h is columns h width .. of out, with its own width rows of w1 (double_mlp's
+ * Unflatten(1, (2, width))).  Rows are row-major fp32 with explicit row strides; only the first k_in (heads width) floats of a row are
+ * read or written.  kt = ceil(width / 32), kk = ceil(k_in / 32), Wp = 32 kt.
+ *   msmp_packed_mlp_train_floats = 1536 (2 heads kt kk + (layers == 2 ? 2 kt^2 : 0)) + layers heads Wp: the forward fragments of w1 (, w2),
+ *   the transposed fragments for the data gradients, and the biases, written by ONE msmp_pack_mlp_train_f32 launch;
+ *   msmp_mlp_train_saved_floats = layers heads n_rows Wp: the pre-activations z1 (, z2; one layer: z of each head), every element written.
+ * The size entries return 0 (and msmp_last_error) for a shape outside the range or n_rows outside 1 .. 2^31 - 1.  The launch entries
+ * return MSMP_ERR_UNSUPPORTED for width or k_in outside 1..256, layers outside 1..2, heads outside 1..2 or two heads of two layers;
+ * MSMP_ERR_ARG for a null required pointer, n_rows outside 1 .. 2^31 - 1, a row stride shorter than its row or a blob / saved that is
+ * not 16-byte aligned.  A row's results depend on nothing but that row; two calls give the same bits. */
+int64_t msmp_packed_mlp_train_floats(int layers, int heads, int k_in, int width);
+int msmp_pack_mlp_train_f32(const float* w1, const float* b1, const float* w2, const float* b2, int layers, int heads, int k_in, int width,
+                            float* packed_out, msmp_stream_t stream);
+int64_t msmp_mlp_train_saved_floats(int64_t n_rows, int layers, int heads, int width);
+/* x [n_rows, ldx] -> out [n_rows, ld_out] and saved. */
+int msmp_mlp_train_fwd_f32(const float* x, int ldx, int64_t n_rows, int layers, int heads, int k_in, int width, const float* packed,
+                           float* saved, float* out, int ld_out, msmp_stream_t stream);
+/* grad_out [n_rows, ld_grad] (the gradient of out), the forward's x and saved -> dw1, db1 (, dw2, db2) in the layouts of the parameters,
+ * every element written, and, where dx is not NULL, dx [n_rows, ld_dx] = the gradient of x (two heads: the sum over the heads, accumulated
+ * in head order).  One kernel launch computes dz2 = grad_out dswish(z2), da1 = w2^T dz2, dz1 = da1 dswish(z1) and dx = w1^T dz1 and leaves
+ * dz2, dz1 and a1 = Swish(z1) in the workspace as row matrices of row stride 128 ceil(width / 128) (dz1 of two heads: 128 ceil(2 width /
+ * 128)) with zeros in the padding columns; the weight gradients are then msmp_grad_weights_f32 jobs of 128 columns of dz each, issued
+ * inside this call (fixed summation order), and one small copy for a part-filled last 128-row group.  No atomics, no memset, no
+ * synchronisation, capturable.  workspace: msmp_mlp_train_bwd_workspace_bytes bytes (0 for a shape outside the range); MSMP_ERR_WORKSPACE
+ * if workspace_bytes is below it. */
+size_t msmp_mlp_train_bwd_workspace_bytes(int64_t n_rows, int layers, int heads, int k_in, int width);
+int msmp_mlp_train_bwd_f32(const float* grad_out, int ld_grad, const float* x, int ldx, const float* saved, int64_t n_rows, int layers,
+                           int heads, int k_in, int width, const float* packed, float* dx, int ld_dx, float* dw1, float* db1, float* dw2,
+                           float* db2, void* workspace, size_t workspace_bytes, msmp_stream_t stream);
 /* The message half of one head at any hidden width 1 <= width <= 256 in ONE launch, nothing edge-sized in memory
  * (experiments/models_gnn.py:132-138 message with message_net_1 factorised per node into p / q, :107 aggr = 'mean'):
  *   agg_out[n][c] = (1 / max(deg n, 1)) sum_{r in CSR row n} Swish(b2[c] + sum_k w2[c][k] Swish(p[n][k] + q[col[r]][k])),   c < width,

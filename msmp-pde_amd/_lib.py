@@ -24,7 +24,7 @@ MSMP_LAYER_LIN = 1
 MSMP_ERR_UNSUPPORTED = -2
 MSMP_MAX_VARS = 8
 HIDDEN = 128
-MSMP_ABI_VERSION = 420          # include/msmp_pde.h: the library must report exactly this
+MSMP_ABI_VERSION = 430          # include/msmp_pde.h: the library must report exactly this
 MSMP_STATUS_INPUT_RANGE, MSMP_STATUS_NODE_SATURATED, MSMP_STATUS_NONFINITE = 1, 2, 4
 
 # name -> (restype, argtypes); must list every symbol include/msmp_pde.h declares
@@ -114,6 +114,13 @@ SIGNATURES = {
     'msmp_packed_lem_wide_floats': (c_int64, [c_int, c_int]),
     'msmp_pack_lem_wide_f32': (c_int, [c_void_p] * 4 + [c_int, c_int, c_void_p, c_void_p]),
     'msmp_lem_encoder_wide_f32': (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_float] + [c_void_p] * 6),
+    'msmp_packed_mlp_train_floats': (c_int64, [c_int, c_int, c_int, c_int]),
+    'msmp_pack_mlp_train_f32': (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p, c_void_p]),
+    'msmp_mlp_train_saved_floats': (c_int64, [c_int64, c_int, c_int, c_int]),
+    'msmp_mlp_train_fwd_f32': (c_int, [c_void_p, c_int, c_int64] + [c_int] * 4 + [c_void_p] * 3 + [c_int, c_void_p]),
+    'msmp_mlp_train_bwd_workspace_bytes': (c_size_t, [c_int64, c_int, c_int, c_int, c_int]),
+    'msmp_mlp_train_bwd_f32': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64] + [c_int] * 4 + [c_void_p, c_void_p, c_int] + [c_void_p] * 4
+                               + [c_void_p, c_size_t, c_void_p]),
     'msmp_packed_lem_wide_train_floats': (c_int64, [c_int, c_int]),
     'msmp_pack_lem_wide_train_f32': (c_int, [c_void_p] * 4 + [c_int, c_int, c_void_p, c_void_p]),
     'msmp_packed_lem_wide_bwd_floats': (c_int64, [c_int, c_int]),

@@ -37,13 +37,11 @@
 //   saved  [6][N][T][Wp]            planes a2, c, a1, d, y_{t-1}, z'; every element is written (pad channels: dt / 2 in a1, a2; 0 elsewhere)
 //   dG     [N][T][4][ldg]           ldg = 128 ceil(W / 128); gate order g1, g2, g3, lin; columns W .. ldg - 1 are written as 0
 #include "lem_layout.h"
-#include "wide_frags.h"
+#include "train_frags.h"      // the tile, publish, fragment-stream and product pieces (shared with mlp_train_kernel.hip)
 
 namespace msmp {
 
 enum { LWT_A2 = 0, LWT_C = 1, LWT_A1 = 2, LWT_D = 3, LWT_Y = 4, LWT_Z = 5, LWT_PLANES = 6 };
-constexpr int LWT_KTILE_U4 = 2 * 3 * 64;                  // one k-tile of a fragment stream or of a published tensor: [s 2][plane 3][lane 64] u32x4, 6 KB
-constexpr int LWT_KTILE_FLOATS = LWT_KTILE_U4 * 4;
 
 // forward blob (floats), kt = ceil(W / 32), Wp = 32 kt:
 //   rec  [wave ct kt][gate 4: g2, g3, g1, lin][k-tile kc kt][s 2][plane 3: hi, mid, lo][lane 64][8 bf16]: rows 32 ct .. of the gate's recurrent
@@ -87,13 +85,6 @@ __device__ __forceinline__ float lwt_bias(const LemWideTrainPackArgs& a, int g, 
     return m[first + row];
 }
 
-__device__ __forceinline__ void lwt_store_b3(float* base, int64_t frag /* (stream, s) */, int lane, const float (&v)[8]) {
-    const Bf3 f = split_bf16x3(v);
-    u32x4* dst = reinterpret_cast<u32x4*>(base) + frag * 3 * 64 + lane;
-    dst[0] = __builtin_bit_cast(u32x4, f.hi);
-    dst[64] = __builtin_bit_cast(u32x4, f.mid);
-    dst[128] = __builtin_bit_cast(u32x4, f.lo);
-}
 
 // TRANSPOSED = false: the forward blob; true: the backward blob (a.b / a.bz unused).  One thread per (ct, gate, kc, s, lane).
 template <bool TRANSPOSED>
@@ -129,88 +120,10 @@ __global__ __launch_bounds__(256) void pack_lem_wide_train_kernel(LemWideTrainPa
     }
 }
 
-// ---- the pieces both kernels share ------------------------------------------------------------------------------------------------
-
-// one tile of a 16-byte aligned row <-> accumulator registers: register 4 q + m is channel 32 ct + 8 q + 4 hh + m (row_hh = row + 4 hh)
-__device__ __forceinline__ void lwt_tile_load(const float* row_hh, int ct, f32x16& v) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const f32x4 p = *reinterpret_cast<const f32x4*>(row_hh + 32 * ct + 8 * q);
-#pragma unroll
-        for (int m = 0; m < 4; ++m) v[4 * q + m] = p[m];
-    }
-}
-__device__ __forceinline__ void lwt_tile_store(float* row_hh, int ct, const f32x16& v) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        f32x4 p;
-#pragma unroll
-        for (int m = 0; m < 4; ++m) p[m] = v[4 * q + m];
-        *reinterpret_cast<f32x4*>(row_hh + 32 * ct + 8 * q) = p;
-    }
-}
-// the same against a DENSE row of W floats (states, dL/dy_T: any alignment); channels >= W read as 0 and are not written
-__device__ __forceinline__ void lwt_dense_load(const float* row, int ct, int hh, int W, f32x16& v) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int ch = 32 * ct + acc_row(r, hh);
-        v[r] = ch < W ? row[ch] : 0.f;
-    }
-}
-__device__ __forceinline__ void lwt_dense_store(float* row, int ct, int hh, int W, const f32x16& v) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int ch = 32 * ct + acc_row(r, hh);
-        if (ch < W) row[ch] = v[r];
-    }
-}
-
-__device__ __forceinline__ void lwt_publish(u32x4* xf, int ct, int lane, const f32x16& v) {
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        float t[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) t[j] = v[8 * s + j];
-        const Bf3 f = split_bf16x3(t);
-        u32x4* dst = xf + (size_t)((ct * 2 + s) * 3) * 64 + lane;
-        dst[0] = __builtin_bit_cast(u32x4, f.hi);
-        dst[64] = __builtin_bit_cast(u32x4, f.mid);
-        dst[128] = __builtin_bit_cast(u32x4, f.lo);
-    }
-}
-
-struct LwtFrag {
-    u32x4 f[2][3];       // [s][plane] of this wave's 32 rows of one k-tile
-};
-// k-tile i of this wave's stream (4 KT per time step) through BUFFER loads: the descriptor holds the wave's stream base (scalar), the
-// fragment is a scalar offset and the lane one 32-bit vector offset.  With global loads the compiler forms a per-lane 64-bit address for each
-// of the 96 fragments of a time step, hoists them out of the t loop as invariants and spills them (49 scratch stores at the head of the
-// first edition).
-__device__ __forceinline__ void lwt_frag_load(LwtFrag& w, __amdgpu_buffer_rsrc_t stream, int i, unsigned loff) {
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) w.f[s][pl] = __builtin_amdgcn_raw_buffer_load_b128(stream, loff, ((i * 2 + s) * 3 + pl) * 1024, 0);
-}
 template <int KT>
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t lwt_stream(const float* rec, int ct_uniform) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(rec + (size_t)ct_uniform * (4 * KT * LWT_KTILE_FLOATS)), 0, 4 * KT * LWT_KTILE_FLOATS * 4,
                                              0x00027000);
-}
-// acc (tile ct) += W[32 ct .., k-tile kc] * published[k-tile kc]
-__device__ __forceinline__ void lwt_mma(const LwtFrag& w, const u32x4* xf, int kc, int lane, f32x16& acc) {
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        const bf16x8 wh = __builtin_bit_cast(bf16x8, w.f[s][0]), wm = __builtin_bit_cast(bf16x8, w.f[s][1]), wl = __builtin_bit_cast(bf16x8, w.f[s][2]);
-        const u32x4* b = xf + (size_t)((kc * 2 + s) * 3) * 64 + lane;
-        const bf16x8 bh = __builtin_bit_cast(bf16x8, b[0]), bm = __builtin_bit_cast(bf16x8, b[64]), bl = __builtin_bit_cast(bf16x8, b[128]);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, bh, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, bl, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, bm, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, bh, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, bm, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, bh, acc, 0, 0, 0);
-    }
 }
 // one GEMM: the KT k-tiles of gate GRP (stream position) against the tensor currently published.  The k-tile after each one is requested
 // before its MFMAs (the first of the next gate after the last; after gate 3 the stream wraps to the next time step), so a GEMM starts with

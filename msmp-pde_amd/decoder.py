@@ -7,7 +7,7 @@ forward-for-training entry (msmp_decoder*_train_fwd_f32, decoder_kernel.hip), ba
   '2d'        hd [N, 2, 128]             output_mlp                                     the *2D classes at width 128
   'gated'     h  [N, 164]                output_mlp_gate, output_mlp_diff               MSGMP-PDE
   'gated2d'   hd [N, 2, 164]             output_mlp_gate, output_mlp_diff               MSGMP-PDE2D
-(hd = double_mlp(h), which stays a PyTorch module.)  `decode` returns None where the entries refuse the sizes by value; the solvers then
+(hd = double_mlp(h): mlp.swish_mlp, or the PyTorch module.)  `decode` returns None where the entries refuse the sizes by value; the solvers then
 keep their PyTorch ops (solvers._decode).  Switch: msmp_tune("dec_bwd").
 """
 import torch
@@ -40,17 +40,22 @@ class DecoderFunction(torch.autograd.Function):
     def forward(ctx, kind, rows, u, tw, dt, *weights):
         fwd, _, comps, gated = _ENTRIES[kind]
         L = lib()
-        rows = rows.detach().contiguous()
+        rows = rows.detach()
         n, width = rows.shape[0], rows.shape[-1]
+        ld = comps * width
+        if gated and rows.dim() == 3 and n > 1 and rows.stride()[1:] == (width, 1) and rows.stride(0) >= ld:
+            ld = rows.stride(0)         # the rows of mlp.swish_mlp, written at the stride of the width-generic path: read in place
+        else:
+            rows = rows.contiguous()
         w = _f32(weights)
         u = None if u is None else u.detach().contiguous()
         out = torch.empty(n, comps * tw, dtype=torch.float32, device=rows.device)
         if gated:
-            check(getattr(L, fwd)(ptr(rows), comps * width, ptr(u), n, width, tw, *[ptr(t) for t in w], float(dt), ptr(out), current_stream()), fwd)
+            check(getattr(L, fwd)(ptr(rows), ld, ptr(u), n, width, tw, *[ptr(t) for t in w], float(dt), ptr(out), current_stream()), fwd)
         else:
             check(getattr(L, fwd)(ptr(rows), ptr(u), n, tw, *[ptr(t) for t in w], float(dt), ptr(out), current_stream()), fwd)
         ctx.save_for_backward(rows, *([u] if u is not None else []), *w)      # the weights stay alive until the backward has been issued
-        ctx.kind, ctx.tw, ctx.dt, ctx.has_u = kind, tw, float(dt), u is not None
+        ctx.kind, ctx.tw, ctx.dt, ctx.has_u, ctx.ld = kind, tw, float(dt), u is not None, ld
         ctx.dtypes = [p.dtype for p in weights]
         return out
 
@@ -63,12 +68,12 @@ class DecoderFunction(torch.autograd.Function):
         u, w = (rest[0], rest[1:]) if ctx.has_u else (None, rest)
         n, width, tw = rows.shape[0], rows.shape[-1], ctx.tw
         g = grad_out.to(torch.float32).contiguous()
-        dh = torch.empty_like(rows)                                     # every element of every output is written by the kernels
+        dh = torch.empty(rows.shape, dtype=rows.dtype, device=rows.device)      # compact; every element of every output is written by the kernels
         grads = [torch.empty_like(t) for t in w]
         ws = torch.empty(L.msmp_decoder_bwd_workspace_bytes(comps, gated, width, tw), dtype=torch.uint8, device=rows.device)
         tail = [ptr(dh)] + [ptr(t) for t in grads] + [ptr(ws), ws.numel(), current_stream()]
         if gated:
-            rc = getattr(L, bwd)(ptr(g), ptr(rows), comps * width, ptr(u), n, width, tw, *[ptr(t) for t in w], ctx.dt, *tail)
+            rc = getattr(L, bwd)(ptr(g), ptr(rows), ctx.ld, ptr(u), n, width, tw, *[ptr(t) for t in w], ctx.dt, *tail)
         elif comps == 2:
             rc = getattr(L, bwd)(ptr(g), ptr(rows), n, tw, *[ptr(t) for t in w], ctx.dt, *tail)
         else:

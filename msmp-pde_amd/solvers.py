@@ -12,8 +12,8 @@ Reference classes:
 Inference (no autograd) runs on HIP kernels end to end: the encoder (msmp_lem_encoder_nodes_f32 with lemoutput_mlp fused, or
 msmp_mlp2_swish_f32 for embedding_mlp), the L x [message -> mean -> update -> InstanceNorm (-> gate blend)] loop
 (msmp_mp_layer_f32), `double_mlp` of the 2-D classes (msmp_linear_swish_f32) and the decoder CNN with the Euler update
-(msmp_decoder_f32 / msmp_decoder2d_f32).  Under autograd the layers, the LEM encoder and the decoder CNN use their
-HIP forward / backward pairs (autograd.py, lem.py, decoder.py) and the small encoder modules PyTorch-ROCm ops.  `pde.L`,
+(msmp_decoder_f32 / msmp_decoder2d_f32).  Under autograd the layers, the LEM encoder, the decoder CNN and the Swish MLPs around them
+(embedding_mlp, lemoutput_mlp, lstmoutput_mlp, double_mlp) use their HIP forward / backward pairs (autograd.py, lem.py, decoder.py, mlp.py).  `pde.L`,
 `pde.tmax`, `pde.dt` are read at call time (they are mutated after construction, experiments/train.py:355-358).  Compute
 dtype is float32; the result is returned in the dtype of `data.x`.
 """
@@ -29,7 +29,8 @@ from .layers import GNN_Layer, GNN_LayerLin, Swish, mp_layer
 from .lem import LEM, LEMS
 from .reductions import bias_add
 from . import decoder, wide
-from .wide import _wide_fused, lemoutput_mlp
+from .wide import _wide_fused, lemoutput_mlp, row_stride
+from .mlp import swish_mlp
 
 _DECODER = {20: (15, 4, 10), 25: (16, 3, 14), 50: (12, 2, 10)}   # models_gnn.py:210-224; models_gnn2D.py:79-88
 
@@ -253,12 +254,18 @@ class _SolverBase(nn.Module):
                     cols.append(getattr(data, k) / ev[k])
         return torch.cat([c.to(pos_t.dtype) for c in cols], -1)
 
+    def _mlp(self, seq, x, heads=1, ld_out=None):
+        """A Swish MLP under autograd: the HIP training pair (mlp.swish_mlp; switch "mlp_train"), or the PyTorch module where that
+        returns None (switch 0, CPU, float64, nothing requires grad, sizes the entries refuse)."""
+        out = swish_mlp(seq, x, heads, ld_out)
+        return seq(x) if out is None else out
+
     def _encode(self, u, pos_x, pos_t, variables, dt):
         if self.LSTM_ENCODER:           # models_gnn.py:880-887 / 1042-1052; models_gnn2D.py:752-758 / 894-900
-            return self.lstmoutput_mlp(self.embedding_lstm(self._step_inputs(u, pos_x, pos_t, variables, dt).permute(1, 0, 2)))
+            return self._mlp(self.lstmoutput_mlp, self.embedding_lstm(self._step_inputs(u, pos_x, pos_t, variables, dt).permute(1, 0, 2)))
         if not self.LEM_ENCODER:        # models_gnn.py:269-270
             if torch.is_grad_enabled() and any(p.requires_grad for p in self.embedding_mlp.parameters()):
-                return self.embedding_mlp(torch.cat((u, pos_x, variables), -1))      # differentiable PyTorch path
+                return self._mlp(self.embedding_mlp, torch.cat((u, pos_x, variables), -1))      # differentiable path; the input is data: no dx
             return self._embed_hip(u, pos_x, variables)
         lem = self.embedding_lem
         stateless = not isinstance(lem, LEMS)
@@ -270,7 +277,7 @@ class _SolverBase(nn.Module):
         if (stateless and self.hidden_features != 128 and not torch.is_grad_enabled() and y.dtype == torch.float32
                 and lem.rnn.wide_kernel_selected()):       # the GLU classes without grad: the width-generic HIP recurrence + two HIP row GEMMs
             return lemoutput_mlp(self.lemoutput_mlp, y)
-        return self.lemoutput_mlp(y)
+        return self._mlp(self.lemoutput_mlp, y)
 
     def _step_inputs(self, u, pos_x, pos_t, variables, dt):
         """The recurrent encoder's per-step inputs, node-major [N, T, ninp]."""
@@ -524,7 +531,8 @@ class _SolverBase(nn.Module):
         ok = lambda t: t.is_cuda and t.dtype == torch.float32
         if not (ok(h) and ok(u) and not u.requires_grad) or getattr(self, '_dec_bwd_refused', None) == (h.shape[1], tw) or not fused():
             return None
-        rows = self.double_mlp(h) if self.TWO_D else h
+        # double_mlp of the gated kinds: straight into rows of the stride the width-generic path gives them (wide.double_mlp), read in place
+        rows = self._mlp(self.double_mlp, h, 2, row_stride(2 * h.shape[1]) if kind == 'gated2d' else None) if self.TWO_D else h
         out = decoder.decode(kind, rows, None if self.RETURN_DIFF else u, tw, self.pde.dt, *nets)
         if out is None:
             self._dec_bwd_refused = (h.shape[1], tw)
@@ -537,7 +545,7 @@ class _SolverBase(nn.Module):
             if out is not None:
                 return out.to(u_in.dtype)
         if self.TWO_D and grad_path:    # models_gnn2D.py:125-141
-            diff = _decoder_autograd(self.double_mlp(h), self.output_mlp[0], self.output_mlp[2])
+            diff = _decoder_autograd(self._mlp(self.double_mlp, h, 2), self.output_mlp[0], self.output_mlp[2])
             out = (u.view(-1, 2, tw) + dt.view(1, 1, tw) * diff).flatten(1, 2)
         elif self.TWO_D:                # fused: conv(2->8) -> Swish -> conv(8->2) -> u + cumsum(dt) * diff
             hd = self._double_mlp_hip(h)
@@ -734,7 +742,7 @@ class _GLUBase(_SolverBase):
             return out.to(u_in.dtype)
         half = h.shape[1] // 2
         if self.TWO_D:                  # models_gnn2D.py:1349-1366
-            hd = self.double_mlp(h)                                             # [N, 2, W]
+            hd = self._mlp(self.double_mlp, h, 2)                                   # [N, 2, W]
             half = hd.shape[2] // 2
             diff = self.output_mlp_diff(hd[:, :, half:])
             scale = self.output_mlp_gate(hd[:, :, :half])
