@@ -11,8 +11,8 @@ Reference classes:
   MP_PDE_SolverLEMLin / MP_PDE_Solver2DLEMLin   models_gnn.py:619-756 / models_gnn2D.py:920-1057   ("LEM" / "LEM2D" ablations)
 Inference (no autograd) runs on HIP kernels end to end: the encoder (msmp_lem_encoder_nodes_f32 with lemoutput_mlp fused, or
 msmp_mlp2_swish_f32 for embedding_mlp), the L x [message -> mean -> update -> InstanceNorm (-> gate blend)] loop
-(msmp_mp_layer_f32), `double_mlp` of the 2-D classes (msmp_linear_swish_f32) and the decoder CNN with the Euler update
-(msmp_decoder_f32 / msmp_decoder2d_f32).  Under autograd the layers, the LEM encoder, the decoder CNN and the Swish MLPs around them
+(msmp_mp_layer_f32), then `double_mlp` of the 2-D classes and the decoder CNN with the Euler update (decoder.py: `decode_state` chooses
+every class's decode route).  Under autograd the layers, the LEM encoder, the decoder CNN and the Swish MLPs around them
 (embedding_mlp, lemoutput_mlp, lstmoutput_mlp, double_mlp) use their HIP forward / backward pairs (autograd.py, lem.py, decoder.py, mlp.py).  `pde.L`,
 `pde.tmax`, `pde.dt` are read at call time (they are mutated after construction, experiments/train.py:355-358).  Compute
 dtype is float32; the result is returned in the dtype of `data.x`.
@@ -28,11 +28,10 @@ from .graph import structure_of
 from .layers import GNN_Layer, GNN_LayerLin, Swish, mp_layer
 from .lem import LEM, LEMS
 from .reductions import bias_add
-from . import decoder, wide
-from .wide import _wide_fused, lemoutput_mlp, row_stride
+from . import decoder
+from .decoder import _Conv1dNoMIOpen        # noqa: F401  (models pickled whole name it here)
+from .wide import _wide_fused, lemoutput_mlp
 from .mlp import swish_mlp
-
-_DECODER = {20: (15, 4, 10), 25: (16, 3, 14), 50: (12, 2, 10)}   # models_gnn.py:210-224; models_gnn2D.py:79-88
 
 
 class _Linear(nn.Linear):
@@ -48,51 +47,6 @@ class _Linear(nn.Linear):
 
 def _lin(i, o):
     return _Linear(i, o, dtype=torch.float32)
-
-
-_TOEPLITZ = {}
-
-
-def _conv1d_as_matmul(x, weight, bias, stride):
-    """Conv1d(x [N, Cin, Lin]; weight [Cout, Cin, k], stride) as ONE dense GEMM [N, Cin Lin] x T [Cin Lin, Cout Lout], T the
-    convolution's Toeplitz matrix, itself the weight times a fixed 0/1 shift tensor (differentiable both ways as small GEMMs).
-    The decoder's convolutions have 1-2 input and 8 output channels: as unfold + einsum they are [N L, 16] x [16, 8] products for
-    which the library picked a 32x16-tile kernel (3.7 ms of a 48-ms training iteration at batch 512, plus the unfold backward);
-    as Toeplitz products they are [N,128] x [128,304] and [N,304] x [304,25]: well-shaped GEMMs forward and backward."""
-    cout, cin, k = weight.shape
-    n, _, lin = x.shape
-    lout = (lin - k) // stride + 1
-    key = (k, lin, stride, x.device, weight.dtype)
-    if key not in _TOEPLITZ:
-        # E[tap, i, l] = 1 where input position i feeds output position l through that tap (i = stride l + tap): T = w . E is a
-        # [Cout Cin, k] x [k, Lin Lout] product forward and backward (a gather's backward would be a sorted index_put, a dense
-        # selection matrix over all of T's entries a 20-MB GEMV per call)
-        i = torch.arange(lin, device=x.device)[None, :, None]
-        l = torch.arange(lout, device=x.device)[None, None, :]
-        tap = torch.arange(k, device=x.device)[:, None, None]
-        _TOEPLITZ[key] = (i == stride * l + tap).to(weight.dtype).reshape(k, lin * lout)
-    t = (weight.reshape(cout * cin, k) @ _TOEPLITZ[key]).view(cout, cin, lin, lout).permute(1, 2, 0, 3).reshape(cin * lin, cout * lout)
-    out = x.reshape(n, cin * lin) @ t
-    return bias_add(out, bias, lout).view(n, cout, lout)
-
-
-def _decoder_autograd(x, conv1, conv2):
-    """output_mlp (Conv1d -> Swish -> Conv1d) for the AUTOGRAD path, written as two Toeplitz GEMMs so that the backward is plain
-    GEMM / elementwise work: MIOpen's implicit-GEMM backward-data kernel for this shape faulted on MI355X
-    (memory access fault inside igemm_bwd_gtcx35_nhwc_fp32, seen with rocgdb).  x [N, Cin, 128] -> [N, Cout, tw]."""
-    mid = _conv1d_as_matmul(x, conv1.weight, conv1.bias, conv1.stride[0])
-    mid = mid * torch.sigmoid(mid)
-    return _conv1d_as_matmul(mid, conv2.weight, conv2.bias, 1)
-
-
-class _Conv1dNoMIOpen(nn.Conv1d):
-    """nn.Conv1d (same parameters and state_dict keys: `weight`, `bias`) whose forward is a Toeplitz GEMM.  Under autograd the
-    library path of these decoder shapes ([N, C, 128], kernel 16 / stride 3 and [N, 8, 38], kernel 14) reaches MIOpen's
-    implicit-GEMM backward-data kernel, which faulted on MI355X (igemm_bwd_gtcx35_nhwc_fp32, round 1); `model.output_mlp(x)`
-    called the reference's way therefore never dispatches a MIOpen convolution, forward or backward."""
-
-    def forward(self, x):
-        return _conv1d_as_matmul(x, self.weight, self.bias, self.stride[0])
 
 
 class _OutEdgeMean(torch.autograd.Function):
@@ -170,19 +124,17 @@ class _SolverBase(nn.Module):
         else:
             self.embedding_mlp = nn.Sequential(_lin(comps * time_window + 2 + len(eq_variables), hidden_features), Swish(),
                                                _lin(hidden_features, hidden_features), Swish())
-        k1, s1, k2 = _DECODER[time_window]
         if self.TWO_D:
             self.double_mlp = nn.Sequential(_lin(hidden_features, 2 * hidden_features), Swish(),
                                             nn.Unflatten(1, (2, hidden_features)))
-        self.output_mlp = nn.Sequential(_Conv1dNoMIOpen(comps, 8, k1, stride=s1, dtype=torch.float32), Swish(),
-                                        _Conv1dNoMIOpen(8, comps, k2, stride=1, dtype=torch.float32))
+        self.output_mlp = decoder.cnn(comps, *decoder._DECODER[time_window])
 
     def __repr__(self):
         return 'GNN'     # every helper of the reference dispatches on this (train_helper.py:99,110,124,...)
 
     # -- feature preparation -----------------------------------------------------------------
     def _variable_columns(self, data):
-        """(tensor [N,1], divisor) of every equation-variable column after pos_t, in the reference's order."""
+        """(tensor [N,1], divisor or None: not divided) of every equation-variable column after pos_t, in the reference's order."""
         ev = self.eq_variables
         cols = []
         if self.TWO_D:      # models_gnn2D.py:112-116 -- NB 'b' divides data.a (reference behaviour, kept)
@@ -196,7 +148,7 @@ class _SolverBase(nn.Module):
                     cols.append((getattr(data, k), ev[k]))
             for k in ('bc_left', 'bc_right'):
                 if k in ev:
-                    cols.append((getattr(data, k), 1))
+                    cols.append((getattr(data, k), None))
             for k in ('c', 'D', 'r'):
                 if k in ev:
                     cols.append((getattr(data, k), ev[k]))
@@ -230,28 +182,12 @@ class _SolverBase(nn.Module):
         check(L.msmp_prepare_nodes(ptr(x), int(x.dtype == torch.float64), ptr(pos), int(pos.dtype == torch.float64), n, tw_feat,
                                    float(self.pde.L), float(self.pde.tmax), nc, (ctypes.c_void_p * max(nc, 1))(*[ptr(c) for c in cs]),
                                    (ctypes.c_int * max(nc, 1))(*[int(c.dtype == torch.float64) for c in cs]),
-                                   (ctypes.c_double * max(nc, 1))(*[float(d) for _, d in cols]), ptr(u), ptr(pos_x), ptr(pos_t),
+                                   (ctypes.c_double * max(nc, 1))(*[1.0 if d is None else float(d) for _, d in cols]), ptr(u), ptr(pos_x), ptr(pos_t),
                                    ptr(variables), ptr(feat), current_stream()), 'msmp_prepare_nodes')
         return u, pos_x, pos_t, variables, feat
 
     def _variables(self, data, pos_t):
-        ev = self.eq_variables
-        cols = [pos_t]
-        if self.TWO_D:      # models_gnn2D.py:112-116 -- NB 'b' divides data.a (reference behaviour, kept)
-            if 'a' in ev:
-                cols.append(data.a / ev['a'])
-            if 'b' in ev:
-                cols.append(data.a / ev['b'])
-        else:               # models_gnn.py:250-266
-            for k in ('alpha', 'beta', 'gamma'):
-                if k in ev:
-                    cols.append(getattr(data, k) / ev[k])
-            for k in ('bc_left', 'bc_right'):
-                if k in ev:
-                    cols.append(getattr(data, k))
-            for k in ('c', 'D', 'r'):
-                if k in ev:
-                    cols.append(getattr(data, k) / ev[k])
+        cols = [pos_t] + [c if d is None else c / d for c, d in self._variable_columns(data)]
         return torch.cat([c.to(pos_t.dtype) for c in cols], -1)
 
     def _mlp(self, seq, x, heads=1, ld_out=None):
@@ -524,64 +460,8 @@ class _SolverBase(nn.Module):
 
         return self._decode(h, u, u_in, dt, tw)
 
-    def _decode_train(self, kind, h, u, tw, fused, *nets):
-        """The decoder under autograd on the HIP kernels (decoder.DecoderFunction: the forward kernel + one backward call), or None where
-        the PyTorch ops apply: switch "dec_bwd" 0 (`fused`: the test of the switches), tensors the kernels do not read, a `u` that
-        requires grad, and sizes the entries refuse by value (remembered: not asked again)."""
-        ok = lambda t: t.is_cuda and t.dtype == torch.float32
-        if not (ok(h) and ok(u) and not u.requires_grad) or getattr(self, '_dec_bwd_refused', None) == (h.shape[1], tw) or not fused():
-            return None
-        # double_mlp of the gated kinds: straight into rows of the stride the width-generic path gives them (wide.double_mlp), read in place
-        rows = self._mlp(self.double_mlp, h, 2, row_stride(2 * h.shape[1]) if kind == 'gated2d' else None) if self.TWO_D else h
-        out = decoder.decode(kind, rows, None if self.RETURN_DIFF else u, tw, self.pde.dt, *nets)
-        if out is None:
-            self._dec_bwd_refused = (h.shape[1], tw)
-        return out
-
     def _decode(self, h, u, u_in, dt, tw):
-        grad_path = torch.is_grad_enabled() and (h.requires_grad or any(p.requires_grad for p in self.output_mlp.parameters()))
-        if grad_path:
-            out = self._decode_train('2d' if self.TWO_D else '1d', h, u, tw, lambda: lib().msmp_tune_query(b'dec_bwd'), self.output_mlp)
-            if out is not None:
-                return out.to(u_in.dtype)
-        if self.TWO_D and grad_path:    # models_gnn2D.py:125-141
-            diff = _decoder_autograd(self._mlp(self.double_mlp, h, 2), self.output_mlp[0], self.output_mlp[2])
-            out = (u.view(-1, 2, tw) + dt.view(1, 1, tw) * diff).flatten(1, 2)
-        elif self.TWO_D:                # fused: conv(2->8) -> Swish -> conv(8->2) -> u + cumsum(dt) * diff
-            hd = self._double_mlp_hip(h)
-            out = torch.empty_like(u)
-            c1, c2 = self.output_mlp[0], self.output_mlp[2]
-            w = [p.detach().to(torch.float32).contiguous() for p in (c1.weight, c1.bias, c2.weight, c2.bias)]   # kept alive
-            check(lib().msmp_decoder2d_f32(ptr(hd), ptr(u), u.shape[0], tw, ptr(w[0]), ptr(w[1]), ptr(w[2]), ptr(w[3]),
-                                           float(self.pde.dt), ptr(out), current_stream()), 'msmp_decoder2d_f32')
-        elif grad_path:
-            diff = _decoder_autograd(h[:, None], self.output_mlp[0], self.output_mlp[2]).squeeze(1)   # differentiable decoder
-            out = diff if self.RETURN_DIFF else u[:, -1:] + dt.view(1, tw) * diff
-        else:                           # models_gnn.py:275-279, fused: conv -> Swish -> conv -> u + cumsum(dt) * diff
-            out = torch.empty_like(u)
-            c1, c2 = self.output_mlp[0], self.output_mlp[2]
-            w = [p.detach().to(torch.float32).contiguous() for p in (c1.weight, c1.bias, c2.weight, c2.bias)]   # kept alive
-            h = h.contiguous()
-            check(lib().msmp_decoder_f32(ptr(h), None if self.RETURN_DIFF else ptr(u), u.shape[0], tw, ptr(w[0]), ptr(w[1]), ptr(w[2]),
-                                         ptr(w[3]), float(self.pde.dt), ptr(out), current_stream()), 'msmp_decoder_f32')
-        return out.to(u_in.dtype)
-
-    def _double_mlp_hip(self, h):
-        """double_mlp (models_gnn2D.py:66-70: Linear(128, 256) + Swish + Unflatten) as one HIP row GEMM with the bias and the Swish in its
-        epilogue (msmp_linear_swish_f32); returns [N, 2, 128]."""
-        lin = self.double_mlp[0]
-        w, b = lin.weight.detach().to(torch.float32).contiguous(), lin.bias.detach().to(torch.float32).contiguous()
-        h = h.contiguous()
-        n_out, k = w.shape
-        need = lib().msmp_linear_swish_workspace_bytes(k, n_out)
-        if not need:
-            raise RuntimeError(f'double_mlp of {k} -> {n_out} features is outside msmp_linear_swish_f32')
-        ws = _Workspace.get(need, h.device)         # per (device, stream); the layers are done with it by now
-        out = torch.empty(h.shape[0], n_out, dtype=torch.float32, device=h.device)
-        check(lib().msmp_linear_swish_f32(ptr(h), h.shape[0], k, ptr(w), ptr(b), n_out, ptr(out), ptr(ws), ws.numel(), current_stream()),
-              'msmp_linear_swish_f32')
-        self._dmlp_keep = (w, b)          # alive until the stream has consumed them
-        return out.view(h.shape[0], 2, n_out // 2)
+        return decoder.decode_state(self, h, u, u_in, dt, tw)
 
     def capture(self, data):
         """hipGraph of `forward` for a fixed graph batch (inference): returns `step(data) -> prediction` that copies the
@@ -695,11 +575,9 @@ class _GLUBase(_SolverBase):
     gated pair of CNNs on the two halves of the hidden state,  out = (1 - scale) u_last + cumsum(dt) scale diff  with
     scale = output_mlp_gate(h[..., :82]), diff = output_mlp_diff(h[..., 82:])  (experiments/models_gnn.py:1379-1523,
     models_gnn2D.py:1198-1366; no sigmoid on `scale`, as in the reference).  Layers: the width-generic HIP path
-    (wide._mp_layer_wide); without grad the LEM recurrence is one HIP launch (msmp_lem_encoder_wide_f32), lemoutput_mlp two HIP row
-    GEMMs, double_mlp one (msmp_linear_f32) and the two small CNNs with the gated update one launch (msmp_decoder_gated_f32 /
-    msmp_decoder2d_gated_f32; switch "wide_dec").  Under autograd the decoder is the same kernel + one backward call
-    (decoder.DecoderFunction; switch "dec_bwd").  With the switches or the fused width-generic path off, and at a width or time window the
-    entries refuse, the decoder is PyTorch-ROCm ops."""
+    (wide._mp_layer_wide); without grad the LEM recurrence is one HIP launch (msmp_lem_encoder_wide_f32) and lemoutput_mlp two HIP row
+    GEMMs.  The decode routes of the gated kinds (one launch without grad, kernel + one backward call under autograd, PyTorch-ROCm ops
+    otherwise) are in the table of decoder.decode_state."""
     GATED, LEM_ENCODER, LAYER = True, True, GNN_LayerLin
 
     def __init__(self, pde, time_window=25, hidden_features=164, hidden_layer=6, eq_variables={}, save_state=None):
@@ -707,51 +585,10 @@ class _GLUBase(_SolverBase):
         comps = 2 if self.TWO_D else 1
         assert time_window == 25, 'the GLU decoder of the reference exists for time_window 25 (Conv1d(.., 8, 6, stride 2) -> Conv1d(8, .., 15) on 82 features)'
         del self.output_mlp
-        mk = lambda: nn.Sequential(_Conv1dNoMIOpen(comps, 8, 6, stride=2, dtype=torch.float32), Swish(),
-                                   _Conv1dNoMIOpen(8, comps, 15, stride=1, dtype=torch.float32))
         # registration order = order of state_dict() and parameters(), which an optimizer.state_dict() is indexed by: the 1-D reference
         # class registers gate, then diff (models_gnn.py), the 2-D one diff, then gate (models_gnn2D.py:1291-1295)
         for name in (('output_mlp_diff', 'output_mlp_gate') if self.TWO_D else ('output_mlp_gate', 'output_mlp_diff')):
-            setattr(self, name, mk())
-
-    def _decode_hip(self, h, u, tw):
-        """The decoder as one HIP launch (2-D: behind double_mlp as one row GEMM), or None where the PyTorch ops below apply: under
-        autograd, for tensors the kernels do not read, with the switch "wide_dec" (or any switch of the fused width-generic path) off,
-        and at sizes the entry refuses by value."""
-        mods = (self.output_mlp_gate, self.output_mlp_diff) + ((self.double_mlp,) if self.TWO_D else ())
-        grad_path = torch.is_grad_enabled() and (h.requires_grad or any(p.requires_grad for m in mods for p in m.parameters()))
-        if grad_path or not (h.is_cuda and h.dtype == torch.float32 and u.is_cuda and u.dtype == torch.float32):
-            return None
-        W = h.shape[1]
-        if not _wide_fused(b'wide_dec') or getattr(self, '_dec_refused', None) == (W, tw):
-            return None
-        h, u = h.contiguous(), u.contiguous()
-        rows, ld = wide.double_mlp(self.double_mlp[0], h) if self.TWO_D else (h, W)
-        out = None if rows is None else wide.gated_decoder(rows, ld, u, W, tw, self.output_mlp_gate, self.output_mlp_diff, self.pde.dt, self.TWO_D)
-        if out is None:
-            self._dec_refused = (W, tw)         # refused by value: these sizes are not asked again (in 2-D each try costs a row GEMM)
-        return out
-
-    def _decode(self, h, u, u_in, dt, tw):
-        out = self._decode_hip(h, u, tw)
-        mods = (self.output_mlp_gate, self.output_mlp_diff) + ((self.double_mlp,) if self.TWO_D else ())
-        if out is None and torch.is_grad_enabled() and (h.requires_grad or any(p.requires_grad for m in mods for p in m.parameters())):
-            out = self._decode_train('gated2d' if self.TWO_D else 'gated', h, u, tw, lambda: _wide_fused(b'dec_bwd'),
-                                     self.output_mlp_gate, self.output_mlp_diff)
-        if out is not None:
-            return out.to(u_in.dtype)
-        half = h.shape[1] // 2
-        if self.TWO_D:                  # models_gnn2D.py:1349-1366
-            hd = self._mlp(self.double_mlp, h, 2)                                   # [N, 2, W]
-            half = hd.shape[2] // 2
-            diff = self.output_mlp_diff(hd[:, :, half:])
-            scale = self.output_mlp_gate(hd[:, :, :half])
-            out = ((1.0 - scale) * u.view(-1, 2, tw) + dt.view(1, 1, tw) * scale * diff).flatten(1, 2)
-        else:                           # models_gnn.py:1511-1521
-            scale = self.output_mlp_gate(h[:, :half][:, None]).squeeze(1)
-            diff = self.output_mlp_diff(h[:, half:][:, None]).squeeze(1)
-            out = (1.0 - scale) * u[:, -1:] + dt.view(1, tw) * (scale * diff)
-        return out.to(u_in.dtype)
+            setattr(self, name, decoder.cnn(comps, *decoder._DECODER_GLU))
 
 
 class MP_PDE_SolverLEMLinGatedGLU(_GLUBase):

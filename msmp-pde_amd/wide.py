@@ -60,40 +60,6 @@ def lemoutput_mlp(mlp, y):
     return b[:, :W].contiguous()
 
 
-def double_mlp(lin, h):
-    """double_mlp of the 2-D GLU class (models_gnn2D.py:1279-1283: Linear(W, 2 W) + Swish; the Unflatten is a view) at a width other
-    than 128 as one msmp_linear_f32 call with the bias + Swish epilogue (mode 1).  Returns (hd, ld): node n's component c is
-    hd[n, c W : (c + 1) W], rows ld = row_stride(2 W) floats apart -- the buffer the row GEMM writes, which the decoder reads in place.
-    (None, ld) at a width outside msmp_linear_f32."""
-    n, W = h.shape
-    ld = row_stride(2 * W)
-    need = lib().msmp_linear_workspace_bytes(W, 2 * W)
-    if not need:
-        return None, ld
-    w = [p.detach().to(torch.float32).contiguous() for p in (lin.weight, lin.bias)]
-    ws = _Workspace.get(need, h.device)
-    hd = torch.empty(n, ld, dtype=torch.float32, device=h.device)
-    _wide_linear(_padded_rows(h), W, w[0], w[1], 2 * W, 1, hd, ws)
-    hd._msmp_keep = w           # the kernels read the weights after this returns
-    return hd, ld
-
-
-def gated_decoder(rows, ld, u, W, tw, gate, diff, dt, two_d):
-    """The gated CNN decoder of the GLU classes with its Euler update as ONE launch (decoder_kernel.hip: msmp_decoder_gated_f32 on the
-    rows of h, msmp_decoder2d_gated_f32 on those of double_mlp; models_gnn.py:1514-1521, models_gnn2D.py:1355-1366).  gate, diff: the
-    two Conv1d -> Swish -> Conv1d modules.  Returns out [N, comps tw], or None where the entry refuses the sizes by value (a width or
-    time window other than the reference's 164 / 25): the caller keeps its PyTorch ops."""
-    L = lib()
-    w = [p.detach().to(torch.float32).contiguous() for m in (gate, diff) for p in (m[0].weight, m[0].bias, m[2].weight, m[2].bias)]
-    out = torch.empty_like(u)
-    name = 'msmp_decoder2d_gated_f32' if two_d else 'msmp_decoder_gated_f32'
-    rc = getattr(L, name)(ptr(rows), ld, ptr(u), u.shape[0], W, tw, *[ptr(t) for t in w], float(dt), ptr(out), current_stream())
-    if not _entry_taken(name, rc):
-        return None
-    out._msmp_keep = w          # the kernel reads the eight weight tensors after this returns
-    return out
-
-
 def _padded_rows(x):
     """x [N, K] with K zero-padded to a multiple of 4, contiguous: the row layout msmp_linear_f32 reads."""
     pad = (-x.shape[1]) % 4

@@ -130,11 +130,11 @@ def test_rows_are_repeatable_and_independent_of_one_another(mp, shared, comps):
 def test_double_mlp_as_one_row_gemm(mp):
     """double_mlp at width 164 (Linear(164, 328) + Swish) in the form the 2-D class uses: one msmp_linear_f32 call into the 384-float rows
     the decoder reads in place; against float64, bar of test_general_linear_kernel."""
-    from msmp_pde_amd import wide
+    from msmp_pde_amd import decoder
     torch.manual_seed(11)
     lin = torch.nn.Linear(W, 2 * W).cuda()
     h = torch.randn(33, W, device='cuda')
-    hd, ld = wide.double_mlp(lin, h)
+    hd, ld = decoder.double_mlp(lin, h)
     assert ld == 384 and hd.shape == (33, 384)
     ref = O.swish(O.linear(h.double().cpu().numpy(), lin.weight.detach().double().cpu().numpy(), lin.bias.detach().double().cpu().numpy()))
     got = hd.double().cpu().numpy()

@@ -460,11 +460,11 @@ def test_bench_dump_outputs_and_options(tmp_path):
 
 
 def test_decoder_convolution_as_toeplitz_gemm_matches_conv1d():
-    """solvers._conv1d_as_matmul (the AUTOGRAD decoder: Conv1d as one dense GEMM against the convolution's Toeplitz matrix, itself the
+    """decoder._conv1d_as_matmul (the AUTOGRAD decoder: Conv1d as one dense GEMM against the convolution's Toeplitz matrix, itself the
     weight times a fixed shift tensor) against torch.nn.functional.conv1d, forward and all three gradients, for every decoder geometry
     of the reference (models_gnn.py:210-224, models_gnn2D.py:79-88) in float64 on the CPU."""
     import torch
-    from msmp_pde_amd.solvers import _conv1d_as_matmul
+    from msmp_pde_amd.decoder import _conv1d_as_matmul
     torch.manual_seed(0)
     for cin, cout, k, s, lin in [(1, 8, 16, 3, 128), (8, 1, 14, 1, 38), (2, 8, 16, 3, 128), (8, 2, 14, 1, 38), (1, 8, 15, 4, 128), (8, 1, 10, 1, 29),
                                  (1, 8, 12, 2, 128), (8, 1, 10, 1, 59), (2, 8, 12, 2, 128), (8, 2, 10, 1, 59)]:
