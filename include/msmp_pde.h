@@ -52,12 +52,12 @@ extern "C" {
 
 typedef void* msmp_stream_t;
 
-/* ABI version: 430 = the six msmp_*mlp_train* entries and the switch "mlp_train" added; 420 = the five entries of the 128-wide LEM training pair removed (msmp_lem_train_fwd_wide_f32 / _bwd_wide_f32 serve every
+/* ABI version: 440 = the eight msmp_*lstm* entries and the switch "lstm_train" added; 430 = the six msmp_*mlp_train* entries and the switch "mlp_train" added; 420 = the five entries of the 128-wide LEM training pair removed (msmp_lem_train_fwd_wide_f32 / _bwd_wide_f32 serve every
  * width) and the blob of msmp_pack_lem_f32 without its last section, which only that pair read; 410 = msmp_mp_layer_decode_f32 and msmp_decoder_t removed;
  * 400 = round 4 (msmp_tiles_t: listed, period_tiles, period_nodes; msmp_build_tiles writes 3 statistics);
  * 300 = round 3 (msmp_last_status, msmp_tiles_t checked on every entry point that takes one).  Bumped whenever a
  * prototype or a blob layout changes; the ctypes host refuses a library whose version is not the one it was written for. */
-#define MSMP_ABI_VERSION 430
+#define MSMP_ABI_VERSION 440
 int msmp_version(void);
 const char* msmp_last_error(void);
 
@@ -128,6 +128,11 @@ int msmp_last_status(int* flags_out, int reset);
  *             0: the PyTorch module (library GEMMs and elementwise kernels) differentiated by torch.autograd (the entries themselves
  *             do not read the key; any value other than 0 selects the kernels).  CPU tensors, float64, a call in which nothing requires
  *             grad and sizes the entries refuse by value keep the PyTorch ops.  Measured: DESIGN.md section 4.25.
+ *   "lstm_train" 1: the host's LSTM encoder (the LSTM ablation classes) is ONE msmp_lstm_train_fwd_f32 launch, with `saved` and followed by
+ *             msmp_lstm_train_bwd_f32 + one msmp_grad_weights_cat_f32 under autograd, with saved = NULL without; 0 (default): torch.nn.LSTM
+ *             (MIOpen) with and without grad (the entries themselves do not read the key; any value other than 0 selects the kernels).  CPU
+ *             tensors, float64, step inputs that require grad and sizes the entries refuse by value keep torch.nn.LSTM.  Measured, and why it
+ *             ships at 0 although every measured configuration is faster at 1: DESIGN.md section 4.26.
  *   "tile_arith" 1 (default): ranged tiles take their node rows by arithmetic on tile_halo; 0: always through the node list.
  *   "tile_align" 0 (default): the host cuts the node tiles of a batch of identical graphs at graph boundaries only where tile_nodes divides
  *             the graph size; 1: also where it does not (bitwise graph-order / sharding equivariance on knn graphs, 11-20 % more tiles
@@ -623,6 +628,37 @@ int msmp_lem_train_fwd_wide_f32(const float* xin, int64_t n_nodes, int t_len, in
  * reference's use of it, no gradient of the step inputs is produced (:300-302), nor of the initial states (carried constants, :350-353). */
 int msmp_lem_train_bwd_wide_f32(const float* grad_y, const float* saved, const float* y0, const float* z0, int64_t n_nodes, int t_len,
                                 int width, float dt, const float* packed_bwd, float* dg_out, msmp_stream_t stream);
+/* The LSTM encoder of the LSTM ablation classes (lstm_train_kernel.hip): torch.nn.LSTM(ninp, width) -- one layer, unidirectional, no
+ * projection, gate order i, f, g, o (experiments/models_gnn.py:758-767) -- at any hidden width 1 <= width <= 256, for training and
+ * inference, in the fp32-exact three-way bf16 split of the LEM pair above (no input range; the range status is neither read nor raised):
+ *     G = w_hh h + w_ih x_t + (b_ih + b_hh);  i = s(G_i), f = s(G_f), g = tanh(G_g), o = s(G_o);  c' = f c + i g;  h' = o tanh(c')
+ * The forward is the T-step recurrence, saving what the backward needs; the backward is the back-propagation through time down to
+ * dL/dG, of which the parameter gradients are GEMMs over the N*T rows:  d w_hh = dg^T h_{t-1},  d w_ih = dg^T x_t,  d b_ih = d b_hh =
+ * column sums of dg.  Wp = 32 ceil(width / 32), ldg = 128 ceil(width / 128), kt = ceil(width / 32).  Parameters as torch holds them:
+ * w_ih [4 width, ninp], w_hh [4 width, width], b_ih, b_hh [4 width], ninp 1..8;
+ *   msmp_packed_lstm_train_floats = 6144 kt^2 + 1152 kt, msmp_packed_lstm_bwd_floats = 6144 kt^2 floats,
+ * 0 (and msmp_last_error) for a width or ninp outside the range.  All blobs, `saved` and `dg_out` are 16-byte aligned. */
+int64_t msmp_packed_lstm_train_floats(int ninp, int width);
+int msmp_pack_lstm_train_f32(const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, int ninp, int width, float* packed_out,
+                             msmp_stream_t stream);
+int64_t msmp_packed_lstm_bwd_floats(int ninp, int width);
+int msmp_pack_lstm_bwd_f32(const float* w_hh, int ninp, int width, float* packed_out, msmp_stream_t stream);
+/* saved [6][n_nodes][t_len][Wp] floats: i, f, g, o, c_t, h_{t-1} (every element is written; channels width .. Wp - 1 of c and h are zeros);
+ * dg [n_nodes][t_len][4][ldg] floats.  0 (and msmp_last_error) for a width outside 1..256, n_nodes < 0 or t_len < 1. */
+int64_t msmp_lstm_saved_floats(int64_t n_nodes, int t_len, int width);
+int64_t msmp_lstm_dg_floats(int64_t n_nodes, int t_len, int width);
+/* xin [n_nodes, t_len, msmp_lem_input_stride(ninp)]; h0 / c0 [n_nodes, width] (both NULL = zeros) -> h_out = output[-1], c_out (or NULL)
+ * dense [n_nodes, width]; saved NULL: no backward follows (inference: the same bits in h_out / c_out).  MSMP_ERR_UNSUPPORTED for width
+ * outside 1..256 or ninp outside 1..8; MSMP_ERR_ARG for t_len < 1, a null required pointer, one initial state without the other or a
+ * misaligned blob / saved; n_nodes = 0 is a no-op. */
+int msmp_lstm_train_fwd_f32(const float* xin, int64_t n_nodes, int t_len, int ninp, int width, const float* packed, const float* h0,
+                            const float* c0, float* saved, float* h_out, float* c_out, msmp_stream_t stream);
+/* grad_h [n_nodes, width] = dL/dh_T -> dg_out: per node and step the gates (i | f | g | o), ldg columns each, columns width .. ldg - 1
+ * written as 0, so every gate is one or two 128-column A operands (row stride 4 ldg) of msmp_grad_weights_cat_f32 with B = [plane 5 of
+ * saved, row stride Wp | x_t].  c0: the forward's initial cell state (NULL = zeros; h0 is in the saved plane).  No gradient of the step
+ * inputs is produced, nor of the initial states. */
+int msmp_lstm_train_bwd_f32(const float* grad_h, const float* saved, const float* c0, int64_t n_nodes, int t_len, int width,
+                            const float* packed_bwd, float* dg_out, msmp_stream_t stream);
 /* The Swish MLPs around the encoder and decoder for TRAINING (mlp_train_kernel.hip): forward with the pre-activations saved and the whole
  * backward, one kernel launch each, in the fp32-exact three-way bf16 split of the pair above (no input range; the range status is neither
  * read nor raised).  Parameters in nn.Linear's layout (experiments/models_gnn.py: embedding_mlp, lemoutput_mlp, double_mlp):

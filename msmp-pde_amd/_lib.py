@@ -24,7 +24,7 @@ MSMP_LAYER_LIN = 1
 MSMP_ERR_UNSUPPORTED = -2
 MSMP_MAX_VARS = 8
 HIDDEN = 128
-MSMP_ABI_VERSION = 430          # include/msmp_pde.h: the library must report exactly this
+MSMP_ABI_VERSION = 440          # include/msmp_pde.h: the library must report exactly this
 MSMP_STATUS_INPUT_RANGE, MSMP_STATUS_NODE_SATURATED, MSMP_STATUS_NONFINITE = 1, 2, 4
 
 # name -> (restype, argtypes); must list every symbol include/msmp_pde.h declares
@@ -129,6 +129,14 @@ SIGNATURES = {
     'msmp_lem_wide_dg_floats': (c_int64, [c_int64, c_int, c_int]),
     'msmp_lem_train_fwd_wide_f32': (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_float] + [c_void_p] * 7),
     'msmp_lem_train_bwd_wide_f32': (c_int, [c_void_p] * 4 + [c_int64, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    'msmp_packed_lstm_train_floats': (c_int64, [c_int, c_int]),
+    'msmp_pack_lstm_train_f32': (c_int, [c_void_p] * 4 + [c_int, c_int, c_void_p, c_void_p]),
+    'msmp_packed_lstm_bwd_floats': (c_int64, [c_int, c_int]),
+    'msmp_pack_lstm_bwd_f32': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    'msmp_lstm_saved_floats': (c_int64, [c_int64, c_int, c_int]),
+    'msmp_lstm_dg_floats': (c_int64, [c_int64, c_int, c_int]),
+    'msmp_lstm_train_fwd_f32': (c_int, [c_void_p, c_int64, c_int, c_int, c_int] + [c_void_p] * 7),
+    'msmp_lstm_train_bwd_f32': (c_int, [c_void_p] * 3 + [c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'msmp_packed_wide_msg_floats': (c_int64, [c_int]),
     'msmp_pack_wide_msg_f32': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'msmp_wide_message_max_in_degree': (c_int, [c_int]),

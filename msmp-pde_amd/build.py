@@ -23,6 +23,7 @@ SOURCES = {  # file -> extra flags
     'lem_kernel.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form', '-fno-slp-vectorize'],
     'lem_wide_kernel.hip': [],
     'lem_wide_train_kernel.hip': [],
+    'lstm_train_kernel.hip': [],
     'mlp_train_kernel.hip': [],
     'wide_message_kernel.hip': [],
     'wide_node_tail_kernel.hip': [],

@@ -481,6 +481,7 @@ static TuneRow g_tune[] = {
     {"wide_dec", 1, ANY_INT},    // != 0: the host ends the GLU classes' forward in msmp_decoder_gated_f32 / msmp_decoder2d_gated_f32 (decoder_kernel.hip)
     {"dec_bwd", 1, ANY_INT},     // != 0: under autograd the host's decoder takes msmp_*_train_fwd_f32 + msmp_*_bwd_f32 (decoder_bwd_kernel.hip); 0: PyTorch ops
     {"mlp_train", 1, ANY_INT},   // != 0: under autograd the host's Swish MLPs take msmp_mlp_train_fwd_f32 + msmp_mlp_train_bwd_f32 (mlp_train_kernel.hip); 0: PyTorch ops
+    {"lstm_train", 0, ANY_INT},  // != 0: the host's LSTM encoder takes msmp_lstm_train_fwd_f32 (+ msmp_lstm_train_bwd_f32 under autograd; lstm_train_kernel.hip); 0: torch.nn.LSTM
 };
 #undef ANY_INT
 #undef ON_OFF

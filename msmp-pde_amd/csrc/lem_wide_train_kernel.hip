@@ -120,27 +120,6 @@ __global__ __launch_bounds__(256) void pack_lem_wide_train_kernel(LemWideTrainPa
     }
 }
 
-template <int KT>
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t lwt_stream(const float* rec, int ct_uniform) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(rec + (size_t)ct_uniform * (4 * KT * LWT_KTILE_FLOATS)), 0, 4 * KT * LWT_KTILE_FLOATS * 4,
-                                             0x00027000);
-}
-// one GEMM: the KT k-tiles of gate GRP (stream position) against the tensor currently published.  The k-tile after each one is requested
-// before its MFMAs (the first of the next gate after the last; after gate 3 the stream wraps to the next time step), so a GEMM starts with
-// its first k-tile in registers.  wA / wB alternate by stream index (4 KT is even: index 0 is always wA).
-template <int KT, int GRP>
-__device__ __forceinline__ void lwt_gemm(LwtFrag& wA, LwtFrag& wB, __amdgpu_buffer_rsrc_t stream, const u32x4* xf, int lane, unsigned loff, f32x16& acc) {
-#pragma unroll
-    for (int kc = 0; kc < KT; ++kc) {
-        const int i = GRP * KT + kc;
-        LwtFrag& cur = (i & 1) ? wB : wA;
-        LwtFrag& nxt = (i & 1) ? wA : wB;
-        lwt_frag_load(nxt, stream, (i + 1) % (4 * KT), loff);
-        lwt_mma(cur, xf, kc, lane, acc);
-        __builtin_amdgcn_sched_barrier(0);       // one k-tile of weight fragments ahead, not all of them
-    }
-}
-
 struct LemWideTrainArgs {
     const float* xin;       // [N, T, stride]
     long n_nodes;

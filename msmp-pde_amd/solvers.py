@@ -12,8 +12,10 @@ Reference classes:
 Inference (no autograd) runs on HIP kernels end to end: the encoder (msmp_lem_encoder_nodes_f32 with lemoutput_mlp fused, or
 msmp_mlp2_swish_f32 for embedding_mlp), the L x [message -> mean -> update -> InstanceNorm (-> gate blend)] loop
 (msmp_mp_layer_f32), then `double_mlp` of the 2-D classes and the decoder CNN with the Euler update (decoder.py: `decode_state` chooses
-every class's decode route).  Under autograd the layers, the LEM encoder, the decoder CNN and the Swish MLPs around them
-(embedding_mlp, lemoutput_mlp, lstmoutput_mlp, double_mlp) use their HIP forward / backward pairs (autograd.py, lem.py, decoder.py, mlp.py).  `pde.L`,
+every class's decode route).  The LSTM ablation classes' encoder is torch.nn.LSTM (MIOpen) by default; with msmp_tune("lstm_train", 1) it is one
+launch as well (msmp_lstm_train_fwd_f32; `LSTM.forward` chooses).
+Under autograd the layers, the LEM encoder (and, with that switch, the LSTM encoder), the decoder CNN and the Swish MLPs around them (embedding_mlp, lemoutput_mlp,
+lstmoutput_mlp, double_mlp) use their HIP forward / backward pairs (autograd.py, lem.py, lstm.py, decoder.py, mlp.py).  `pde.L`,
 `pde.tmax`, `pde.dt` are read at call time (they are mutated after construction, experiments/train.py:355-358).  Compute
 dtype is float32; the result is returned in the dtype of `data.x`.
 """
@@ -27,6 +29,7 @@ from ._lib import lib, check, ptr, current_stream, PARAM_EPOCH, PackedCache, cac
 from .graph import structure_of
 from .layers import GNN_Layer, GNN_LayerLin, Swish, mp_layer
 from .lem import LEM, LEMS
+from . import lstm
 from .reductions import bias_add
 from . import decoder
 from .decoder import _Conv1dNoMIOpen        # noqa: F401  (models pickled whole name it here)
@@ -72,16 +75,53 @@ class _OutEdgeMean(torch.autograd.Function):
 
 class LSTM(nn.Module):
     """experiments/models_gnn.py:758-767: torch.nn.LSTM(ninp, nhid), returns output[-1].  Parameter names as the reference's
-    (`rnn.weight_ih_l0` ...)."""
+    (`rnn.weight_ih_l0` ...): `rnn` is an nn.LSTM and stays the parameter holder, so state_dict keys and whole-model pickles are the
+    reference's.  `forward` is where the route is chosen (the table is in its docstring)."""
 
     def __init__(self, ninp, nhid):
         super().__init__()
         self.ninp, self.nhid = ninp, nhid
         self.rnn = nn.LSTM(ninp, nhid)
+        self._packed = PackedCache()
 
-    def forward(self, inputs):
-        output, _ = self.rnn(inputs.contiguous())
+    def _blob(self):
+        cache = self.__dict__.get('_packed')
+        if cache is None:       # a module pickled before the native route existed
+            cache = self._packed = PackedCache()
+        return lstm.packed(cache, self.rnn)
+
+    def forward(self, inputs, states=None, nodes=None):
+        """inputs [T, N, ninp] (the reference's layout), or `nodes` [N, T, ninp] (the layout the kernels read; `inputs` is then None);
+        states = (h0, c0), each [N, nhid], or None (zeros) -> output[-1] = h_T [N, nhid].  The one place where the route is chosen.  With
+        "native" = module and inputs fp32 on the GPU, N > 0, ninp <= 8, width <= 256, inputs (and states) not requiring grad, msmp_tune
+        "lstm_train" != 0, and "backward" = grad enabled and a parameter requires grad:
+
+            native, backward      lstm._LSTMTrainFunction (msmp_lstm_train_fwd_f32 with `saved`, then msmp_lstm_train_bwd_f32 +
+                                  one msmp_grad_weights_cat_f32)
+            native, no backward   msmp_lstm_train_fwd_f32 with saved = NULL (no_grad, or all parameters frozen): one launch, the same bits
+            everything else       self.rnn(...), i.e. torch.nn.LSTM, exactly as before the kernels existed (CPU, float64, switch 0, inputs
+                                  that require grad, sizes outside the kernels' range)
+        """
+        x = inputs if nodes is None else nodes
+        r = self.rnn
+        ps = [r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0]
+        h0, c0 = states if states is not None else (None, None)
+        xin = x.permute(1, 0, 2) if nodes is None else x       # node-major [N, T, ninp] (a view)
+        data = [t for t in (x, h0, c0) if t is not None]
+        fp32_data = all(t.is_cuda and t.dtype == torch.float32 and not t.requires_grad for t in data)
+        fp32_module = all(p.is_cuda and p.dtype == torch.float32 for p in ps)
+        in_range = xin.shape[0] > 0 and lstm.kernel_exists(self.ninp, self.nhid)
+        if fp32_data and fp32_module and in_range and lib().msmp_tune_query(b'lstm_train') != 0:      # native
+            if torch.is_grad_enabled() and any(p.requires_grad for p in ps):
+                return lstm._LSTMTrainFunction.apply(self._blob(), xin, *ps, h0, c0)[0]
+            return lstm.train_forward(self._blob(), self.ninp, self.nhid, lstm._padded_inputs(xin), lstm._state(h0), lstm._state(c0))[0]
+        x = (x if nodes is None else x.permute(1, 0, 2)).contiguous()
+        output, _ = self.rnn(x) if states is None else self.rnn(x, (h0[None], c0[None]))
         return output[-1]
+
+    def forward_nodes(self, xin, states=None):
+        """Same with node-major step inputs xin [N, T, ninp]: the native route reads them as they are."""
+        return self(None, states, nodes=xin)
 
 
 class _SolverBase(nn.Module):
@@ -89,7 +129,7 @@ class _SolverBase(nn.Module):
     GATED = False
     LEM_ENCODER = False
     ALWAYS_SAVE = False     # MP_PDE_SolverLEMLinGatedSave: LEMS regardless of the constructor argument
-    LSTM_ENCODER = False    # the LSTM ablations: torch.nn.LSTM (MIOpen) in place of the LEM, everything after it unchanged
+    LSTM_ENCODER = False    # the LSTM ablations: an LSTM (solvers.LSTM: torch.nn.LSTM / MIOpen by default, the kernels of lstm_train_kernel.hip with msmp_tune("lstm_train", 1)) in place of the LEM, everything after it unchanged
     G2 = False
     RETURN_DIFF = False     # MSSMP_PDE_Solver_sub: forward returns the decoder output, not the Euler update
     LAYER = GNN_Layer
@@ -198,7 +238,7 @@ class _SolverBase(nn.Module):
 
     def _encode(self, u, pos_x, pos_t, variables, dt):
         if self.LSTM_ENCODER:           # models_gnn.py:880-887 / 1042-1052; models_gnn2D.py:752-758 / 894-900
-            return self._mlp(self.lstmoutput_mlp, self.embedding_lstm(self._step_inputs(u, pos_x, pos_t, variables, dt).permute(1, 0, 2)))
+            return self._mlp(self.lstmoutput_mlp, self.embedding_lstm.forward_nodes(self._step_inputs(u, pos_x, pos_t, variables, dt)))
         if not self.LEM_ENCODER:        # models_gnn.py:269-270
             if torch.is_grad_enabled() and any(p.requires_grad for p in self.embedding_mlp.parameters()):
                 return self._mlp(self.embedding_mlp, torch.cat((u, pos_x, variables), -1))      # differentiable path; the input is data: no dx
