@@ -52,12 +52,12 @@ extern "C" {
 
 typedef void* msmp_stream_t;
 
-/* ABI version: 440 = the eight msmp_*lstm* entries and the switch "lstm_train" added; 430 = the six msmp_*mlp_train* entries and the switch "mlp_train" added; 420 = the five entries of the 128-wide LEM training pair removed (msmp_lem_train_fwd_wide_f32 / _bwd_wide_f32 serve every
+/* ABI version: 450 = msmp_g2_gate_blend_f32, msmp_g2_gate_blend_bwd_workspace_bytes, msmp_g2_gate_blend_bwd_f32 and the switch "g2_gate" added; 440 = the eight msmp_*lstm* entries and the switch "lstm_train" added; 430 = the six msmp_*mlp_train* entries and the switch "mlp_train" added; 420 = the five entries of the 128-wide LEM training pair removed (msmp_lem_train_fwd_wide_f32 / _bwd_wide_f32 serve every
  * width) and the blob of msmp_pack_lem_f32 without its last section, which only that pair read; 410 = msmp_mp_layer_decode_f32 and msmp_decoder_t removed;
  * 400 = round 4 (msmp_tiles_t: listed, period_tiles, period_nodes; msmp_build_tiles writes 3 statistics);
  * 300 = round 3 (msmp_last_status, msmp_tiles_t checked on every entry point that takes one).  Bumped whenever a
  * prototype or a blob layout changes; the ctypes host refuses a library whose version is not the one it was written for. */
-#define MSMP_ABI_VERSION 440
+#define MSMP_ABI_VERSION 450
 int msmp_version(void);
 const char* msmp_last_error(void);
 
@@ -133,6 +133,11 @@ int msmp_last_status(int* flags_out, int reset);
  *             (MIOpen) with and without grad (the entries themselves do not read the key; any value other than 0 selects the kernels).  CPU
  *             tensors, float64, step inputs that require grad and sizes the entries refuse by value keep torch.nn.LSTM.  Measured, and why it
  *             ships at 0 although every measured configuration is faster at 1: DESIGN.md section 4.26.
+ *   switch "g2_gate" 1 (default): the host's gradient-gated pair (MP_PDE_Solver2DLEMLinG2) evaluates the gate statistic, tanh and blend
+ *             between its two layer calls as ONE msmp_g2_gate_blend_f32 launch, under autograd with tau saved and msmp_g2_gate_blend_bwd_f32 as
+ *             its backward; 0: PyTorch-ROCm ops around msmp_scatter_mean_f32 (about 14 launches and five [E, width] tensors per pair),
+ *             differentiated by torch.autograd (the entries themselves do not read the key; any value other than 0 selects the kernels).  CPU
+ *             tensors, float64 and widths the entries refuse by value keep the PyTorch ops.  Measured: DESIGN.md section 4.27.
  *   "tile_arith" 1 (default): ranged tiles take their node rows by arithmetic on tile_halo; 0: always through the node list.
  *   "tile_align" 0 (default): the host cuts the node tiles of a batch of identical graphs at graph boundaries only where tile_nodes divides
  *             the graph size; 1: also where it does not (bitwise graph-order / sharding equivariance on knn graphs, 11-20 % more tiles
@@ -659,6 +664,34 @@ int msmp_lstm_train_fwd_f32(const float* xin, int64_t n_nodes, int t_len, int ni
  * inputs is produced, nor of the initial states. */
 int msmp_lstm_train_bwd_f32(const float* grad_h, const float* saved, const float* c0, int64_t n_nodes, int t_len, int width,
                             const float* packed_bwd, float* dg_out, msmp_stream_t stream);
+/* The gradient gate (G2) of MP_PDE_Solver2DLEMLinG2 between the two layer calls of a pair (g2_gate_kernel.hip; experiments/models_gnn2D.py:598-611).
+ * h, gate (the gate layer's output after its InstanceNorm), main (the main layer's output), out, tau_out and every row tensor of the
+ * backward are [n_nodes, ld] fp32, 16-byte aligned, ONE row stride ld for all of them; columns width .. ld - 1 are neither read nor written.
+ * out_rowptr [n_nodes + 1] / out_nbr [n_edges]: node i's out-edges as the TARGETS of the edges regrouped by source (GraphStructure.by_source():
+ * ascending CSR edge id inside a source); in_rowptr / in_col: the CSR by target of msmp_build_csr (rowptr, col).  With t = Swish(gate) and
+ * D_i = max(|out(i)|, 1):
+ *     m_i = (1 / D_i) sum_{j in out(i)} (t_i - t_j)^2,   tau_i = tanh(m_i),   out_i = (1 - tau_i) h_i + tau_i Swish(main_i)
+ * summed edge by edge in list order (square and add rounded separately), then times 1 / D_i: multi-edges count with their multiplicity, a
+ * self-loop contributes an exact 0, a node without out-edges gets tau = 0 and out = h exactly; n_edges = 0 is valid (the list pointers must
+ * still be non-null).  One launch; Swish(gate_j) is recomputed per edge, nothing edge-sized but the int32 list is read or written.  tau_out
+ * NULL: tau is not saved (no backward follows; the same bits in out).  Plain fp32: no input range, the range status is neither read nor
+ * raised.  Timed under MSMP_K_NORM.  Accepted: width a multiple of 4 in 4 .. 256 (anything else MSMP_ERR_UNSUPPORTED before any launch); a
+ * null or misaligned pointer, ld < width or not a multiple of 4, n_nodes outside 1 .. 2^31 - 1 or n_edges outside 0 .. 2^31 - 1: MSMP_ERR_ARG
+ * with msmp_last_error naming the entry and the argument. */
+int msmp_g2_gate_blend_f32(const float* h, const float* gate, const float* main, int ld, const int32_t* out_rowptr, const int32_t* out_nbr,
+                           int64_t n_nodes, int64_t n_edges, int width, float* out, float* tau_out, msmp_stream_t stream);
+/* Its backward from grad_out = dL/dout and the forward's inputs and tau_out:
+ *     dh_i = (1 - tau_i) g_i,   db_i = tau_i g_i Swish'(main_i),   q_i = g_i (Swish(main_i) - h_i) (1 - tau_i^2) / D_i,
+ *     da_i = Swish'(gate_i) (2 q_i sum_{j in out(i)} (t_i - t_j) - 2 sum_{s in in(i)} q_s (t_s - t_i))
+ * as two launches inside the call: a node pass (dh, db, and q into the workspace: n_nodes * width floats) and a gather pass over both
+ * lists in list order (da).  No atomics, no memset, no host read-back, fixed summation order: capturable, and two calls give the same bits.
+ * Every element of columns 0 .. width - 1 of dh, da, db is written.  msmp_g2_gate_blend_bwd_workspace_bytes returns 0 (and
+ * msmp_last_error) for a width or n_nodes outside the range; MSMP_ERR_WORKSPACE if workspace_bytes is below it; other refusals as the forward's. */
+size_t msmp_g2_gate_blend_bwd_workspace_bytes(int64_t n_nodes, int width);
+int msmp_g2_gate_blend_bwd_f32(const float* grad_out, const float* h, const float* gate, const float* main, const float* tau, int ld,
+                               const int32_t* out_rowptr, const int32_t* out_nbr, const int32_t* in_rowptr, const int32_t* in_col,
+                               int64_t n_nodes, int64_t n_edges, int width, float* dh, float* da, float* db, void* workspace,
+                               size_t workspace_bytes, msmp_stream_t stream);
 /* The Swish MLPs around the encoder and decoder for TRAINING (mlp_train_kernel.hip): forward with the pre-activations saved and the whole
  * backward, one kernel launch each, in the fp32-exact three-way bf16 split of the pair above (no input range; the range status is neither
  * read nor raised).  Parameters in nn.Linear's layout (experiments/models_gnn.py: embedding_mlp, lemoutput_mlp, double_mlp):

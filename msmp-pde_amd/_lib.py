@@ -24,7 +24,7 @@ MSMP_LAYER_LIN = 1
 MSMP_ERR_UNSUPPORTED = -2
 MSMP_MAX_VARS = 8
 HIDDEN = 128
-MSMP_ABI_VERSION = 440          # include/msmp_pde.h: the library must report exactly this
+MSMP_ABI_VERSION = 450          # include/msmp_pde.h: the library must report exactly this
 MSMP_STATUS_INPUT_RANGE, MSMP_STATUS_NODE_SATURATED, MSMP_STATUS_NONFINITE = 1, 2, 4
 
 # name -> (restype, argtypes); must list every symbol include/msmp_pde.h declares
@@ -137,6 +137,10 @@ SIGNATURES = {
     'msmp_lstm_dg_floats': (c_int64, [c_int64, c_int, c_int]),
     'msmp_lstm_train_fwd_f32': (c_int, [c_void_p, c_int64, c_int, c_int, c_int] + [c_void_p] * 7),
     'msmp_lstm_train_bwd_f32': (c_int, [c_void_p] * 3 + [c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'msmp_g2_gate_blend_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    'msmp_g2_gate_blend_bwd_workspace_bytes': (c_size_t, [c_int64, c_int]),
+    'msmp_g2_gate_blend_bwd_f32': (c_int, [c_void_p] * 5 + [c_int] + [c_void_p] * 4 + [c_int64, c_int64, c_int] + [c_void_p] * 3
+                                   + [c_void_p, c_size_t, c_void_p]),
     'msmp_packed_wide_msg_floats': (c_int64, [c_int]),
     'msmp_pack_wide_msg_f32': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'msmp_wide_message_max_in_degree': (c_int, [c_int]),

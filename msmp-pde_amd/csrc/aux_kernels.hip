@@ -482,6 +482,7 @@ static TuneRow g_tune[] = {
     {"dec_bwd", 1, ANY_INT},     // != 0: under autograd the host's decoder takes msmp_*_train_fwd_f32 + msmp_*_bwd_f32 (decoder_bwd_kernel.hip); 0: PyTorch ops
     {"mlp_train", 1, ANY_INT},   // != 0: under autograd the host's Swish MLPs take msmp_mlp_train_fwd_f32 + msmp_mlp_train_bwd_f32 (mlp_train_kernel.hip); 0: PyTorch ops
     {"lstm_train", 0, ANY_INT},  // != 0: the host's LSTM encoder takes msmp_lstm_train_fwd_f32 (+ msmp_lstm_train_bwd_f32 under autograd; lstm_train_kernel.hip); 0: torch.nn.LSTM
+    {"g2_gate", 1, ANY_INT},     // != 0: the host's gradient-gated pair takes msmp_g2_gate_blend_f32 (+ msmp_g2_gate_blend_bwd_f32 under autograd; g2_gate_kernel.hip); 0: PyTorch ops around msmp_scatter_mean_f32
 };
 #undef ANY_INT
 #undef ON_OFF

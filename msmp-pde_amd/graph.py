@@ -174,6 +174,18 @@ class GraphStructure(object):
             self._by_source32 = (perm.to(torch.int32).contiguous(), rowptr)
         return self._by_source32
 
+    def out_edges32(self):
+        """(out_rowptr int32 [N+1], out_nbr int32 [max(E, 1)]): every node's out-edges as the TARGETS of the edges regrouped by source,
+        out_nbr = tgt[perm] of by_source32(), the lists msmp_g2_gate_blend_f32 and its backward gather over; made once, at first use (a
+        captured training step meets it during its warmup)."""
+        if getattr(self, '_out_edges32', None) is None:
+            perm32, rowptr = self.by_source32()
+            nbr = torch.zeros(max(self.n_edges, 1), dtype=torch.int32, device=rowptr.device)
+            if self.n_edges:
+                nbr[:self.n_edges] = self.tgt[:self.n_edges][perm32.long()]
+            self._out_edges32 = (rowptr, nbr)
+        return self._out_edges32
+
     def matches(self, edge_index, batch):
         return self._key == (edge_index.data_ptr(), tuple(edge_index.shape), edge_index._version,
                              batch.data_ptr(), batch._version)

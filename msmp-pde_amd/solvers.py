@@ -15,7 +15,8 @@ msmp_mlp2_swish_f32 for embedding_mlp), the L x [message -> mean -> update -> In
 every class's decode route).  The LSTM ablation classes' encoder is torch.nn.LSTM (MIOpen) by default; with msmp_tune("lstm_train", 1) it is one
 launch as well (msmp_lstm_train_fwd_f32; `LSTM.forward` chooses).
 Under autograd the layers, the LEM encoder (and, with that switch, the LSTM encoder), the decoder CNN and the Swish MLPs around them (embedding_mlp, lemoutput_mlp,
-lstmoutput_mlp, double_mlp) use their HIP forward / backward pairs (autograd.py, lem.py, lstm.py, decoder.py, mlp.py).  `pde.L`,
+lstmoutput_mlp, double_mlp) use their HIP forward / backward pairs (autograd.py, lem.py, lstm.py, decoder.py, mlp.py), and so does the
+gradient gate of MP_PDE_Solver2DLEMLinG2 between the two layer calls of a pair, with and without grad (g2.py).  `pde.L`,
 `pde.tmax`, `pde.dt` are read at call time (they are mutated after construction, experiments/train.py:355-358).  Compute
 dtype is float32; the result is returned in the dtype of `data.x`.
 """
@@ -35,6 +36,7 @@ from . import decoder
 from .decoder import _Conv1dNoMIOpen        # noqa: F401  (models pickled whole name it here)
 from .wide import _wide_fused, lemoutput_mlp
 from .mlp import swish_mlp
+from .g2 import g2_gate_blend, _OutEdgeMean        # noqa: F401  (_OutEdgeMean: the PyTorch route's mean, kept importable from here)
 
 
 class _Linear(nn.Linear):
@@ -50,27 +52,6 @@ class _Linear(nn.Linear):
 
 def _lin(i, o):
     return _Linear(i, o, dtype=torch.float32)
-
-
-class _OutEdgeMean(torch.autograd.Function):
-    """Mean of a per-edge tensor [E,128] over each node's OUT-edges (torch_scatter `scatter(..., edge_index[0], reduce='mean')`,
-    models_gnn2D.py:607-608) in a fixed summation order: edges regrouped by source once per graph structure, then
-    msmp_scatter_mean_f32.  Nodes without out-edges get 0."""
-
-    @staticmethod
-    def forward(ctx, msg, gs):
-        perm, rowptr = gs.by_source()
-        m = msg.detach().to(torch.float32)[perm].contiguous()
-        out = torch.empty(gs.n_nodes, m.shape[1], dtype=torch.float32, device=m.device)
-        check(lib().msmp_scatter_mean_f32(ptr(m), ptr(rowptr), gs.n_nodes, ptr(out), current_stream()), 'msmp_scatter_mean_f32')
-        ctx.gs = gs
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        perm, rowptr = ctx.gs.by_source()
-        deg = (rowptr[1:] - rowptr[:-1]).clamp(min=1).to(g.dtype)
-        return (g / deg[:, None])[ctx.gs.col_long], None
 
 
 class LSTM(nn.Module):
@@ -266,13 +247,14 @@ class _SolverBase(nn.Module):
         return torch.cat((pos_x[:, None, :].expand(n, t_len, 1), u[:, :, None],
                           variables[:, None, :].expand(n, t_len, variables.shape[1])), -1)
 
-    def _g2_pair(self, h, u, pos_x, variables, gs, i):
+    def _g2_pair(self, h, u, pos_x, variables, gs, i, feat=None):
         """models_gnn2D.py:606-611 (gradient gating): tau = tanh(mean over the out-edges j -> i of node j of |t_j - t_i|^2) with
         t = Swish(gate layer), then the same blend as the gated classes.  Both layers are the fused HIP layer call
-        (GNN_LayerLin incl. its InstanceNorm); the gate statistic and the blend are PyTorch-ROCm ops."""
-        t = self.swish(mp_layer(h, u, pos_x, variables, gs, self.gnn_layers_gate[i], None))
-        tau = torch.tanh(_OutEdgeMean.apply((t[gs.col_long] - t[gs.tgt_long]) ** 2, gs))
-        return (1.0 - tau) * h + tau * self.swish(mp_layer(h, u, pos_x, variables, gs, self.gnn_layers[i], None))
+        (GNN_LayerLin incl. its InstanceNorm; `feat`: the packed feature rows _forward built, the same bits as without them); the gate
+        statistic, tanh and blend are one more launch (g2.g2_gate_blend chooses the route)."""
+        a = mp_layer(h, u, pos_x, variables, gs, self.gnn_layers_gate[i], None, feat=feat)
+        b = mp_layer(h, u, pos_x, variables, gs, self.gnn_layers[i], None, feat=feat)
+        return g2_gate_blend(h, a, b, gs)
 
     def _embed_packed(self, dev):
         """Packed embedding_mlp weights (msmp_pack_mlp2_f32), cached per parameter version; built on the CURRENT stream."""
@@ -493,7 +475,7 @@ class _SolverBase(nn.Module):
         h = self._encode(u, pos_x, pos_t, variables, dt)
         for i in range(self.hidden_layer):
             if self.G2:
-                h = self._g2_pair(h, u, pos_x, variables, gs, i)
+                h = self._g2_pair(h, u, pos_x, variables, gs, i, feat)
                 continue
             gate = self.gnn_layers_gate[i] if self.GATED else None
             h = mp_layer(h, u, pos_x, variables, gs, self.gnn_layers[i], gate, feat=feat)

@@ -10,7 +10,7 @@ on the HIP forward / native backward path, E2, reference batch size 16 and large
     --ab KEY              A/B of one msmp_tune switch INSIDE the process (the boxes of a pool differ by more than most switches do): per
                           (model, batch) the switch alternates 0, 1, 0, 1, ... for --rounds rounds of --iters timed iterations each; prints
                           the median per setting, their difference, and the spread between two runs of the same setting (the largest
-                          distance of a run from its setting's median).  One of dec_bwd, lem_wide_train, lstm_train, mlp_train, wide_bwd.
+                          distance of a run from its setting's median).  One of dec_bwd, g2_gate, lem_wide_train, lstm_train, mlp_train, wide_bwd.
     --rounds R            alternations of --ab (default 5)
     --captured            with --ab: the iteration as train.CapturedTrainStep replays (one capture per setting) instead of eager"""
 import argparse
@@ -29,7 +29,7 @@ ap.add_argument('--iters', type=int, default=5)
 ap.add_argument('--tune', action='append', default=[])
 ap.add_argument('--torch-adamw', action='store_true')
 ap.add_argument('--exp', default='E2')
-ap.add_argument('--ab', choices=('dec_bwd', 'lem_wide_train', 'lstm_train', 'mlp_train', 'wide_bwd'))
+ap.add_argument('--ab', choices=('dec_bwd', 'g2_gate', 'lem_wide_train', 'lstm_train', 'mlp_train', 'wide_bwd'))
 ap.add_argument('--rounds', type=int, default=5)
 ap.add_argument('--captured', action='store_true')
 args = ap.parse_args()
