@@ -9,7 +9,7 @@
 //   msmp_mlp_train_bwd_f32   dz2 = g dswish(z2);  da1 = W2^T dz2;  dz1 = da1 dswish(z1);  dx = W1^T dz1 (optional: summed over the heads in head order);
 //                            then dW2, db2 = (dz2, a1 = Swish(z1)) and dW1, db1 = (dz1, x) as msmp_grad_weights_f32 jobs of 128 columns of dz each
 //
-// The scheme is lem_wide_train_kernel.hip's with T = 1 (its pieces are in train_frags.h): one 32-row tile per workgroup, KT = ceil(W / 32) waves,
+// The scheme is recurrent_train.h's with T = 1 (its pieces are in train_frags.h): one 32-row tile per workgroup, KT = ceil(W / 32) waves,
 // wave ct owns channel tile ct in accumulator layout (one row per lane); the B operand of a GEMM (x, a1; dz2, dz1) is PUBLISHED in LDS as bf16
 // hi / mid / lo fragments in acc order in ONE area of 6 KT KB reused between barriers, and every wave multiplies its own 32 rows of the weight
 // block -- bf16x3 A fragments streamed from the L2-resident blob through buffer loads, one k-tile ahead -- with the published fragments: six
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256) void pack_mlp_train_kernel(MlpTrainPackArgs a)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int k = 32 * kc + split_k_acc(s, lane >> 5, j);
-            // fragment (row, k) is w[row0 + row][k], transposed w[row0 + k][row]: ONE load from a selected element (see lwt_weight)
+            // fragment (row, k) is w[row0 + row][k], transposed w[row0 + k][row]: ONE load from a selected element (see pack_recurrent_train_kernel)
             const int o = sg.transposed ? k : row, i = sg.transposed ? row : k;
             const bool in = o < sg.n_out && i < sg.n_in;
             const float w = sg.w[in ? (size_t)(sg.row0 + o) * sg.n_in + i : 0];

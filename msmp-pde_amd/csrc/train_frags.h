@@ -1,5 +1,5 @@
 // The bf16x3 fragment pieces of the TRAINING kernels that run one 32-row tile per workgroup with a wave per 32-channel slice
-// (lem_wide_train_kernel.hip, mlp_train_kernel.hip; the scheme is described at the head of the former): accumulator tiles <-> rows, the
+// (the recurrent pairs through recurrent_train.h, whose head describes the scheme, and mlp_train_kernel.hip): accumulator tiles <-> rows, the
 // publish of a B operand as bf16 hi / mid / lo fragments in "acc order", the streamed weight A fragments and the six-MFMA product.
 #pragma once
 #include "wide_frags.h"
@@ -90,30 +90,6 @@ __device__ __forceinline__ void lwt_mma(const LwtFrag& w, const u32x4* xf, int k
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, bh, acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, bm, acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, bh, acc, 0, 0, 0);
-    }
-}
-
-// ---- a T-step recurrence of four gates (lem_wide_train_kernel.hip, lstm_train_kernel.hip): per wave one stream of 4 KT k-tiles per time step ----
-
-// the stream of wave ct: [gate 4 (consumption order)][k-tile KT] k-tiles of LWT_KTILE_FLOATS, 4 KT * LWT_KTILE_FLOATS floats per wave
-template <int KT>
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t lwt_stream(const float* rec, int ct_uniform) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(rec + (size_t)ct_uniform * (4 * KT * LWT_KTILE_FLOATS)), 0, 4 * KT * LWT_KTILE_FLOATS * 4,
-                                             0x00027000);
-}
-// one GEMM: the KT k-tiles of gate GRP (stream position) against the tensor currently published.  The k-tile after each one is requested
-// before its MFMAs (the first of the next gate after the last; after gate 3 the stream wraps to the next time step), so a GEMM starts with
-// its first k-tile in registers.  wA / wB alternate by stream index (4 KT is even: index 0 is always wA).
-template <int KT, int GRP>
-__device__ __forceinline__ void lwt_gemm(LwtFrag& wA, LwtFrag& wB, __amdgpu_buffer_rsrc_t stream, const u32x4* xf, int lane, unsigned loff, f32x16& acc) {
-#pragma unroll
-    for (int kc = 0; kc < KT; ++kc) {
-        const int i = GRP * KT + kc;
-        LwtFrag& cur = (i & 1) ? wB : wA;
-        LwtFrag& nxt = (i & 1) ? wA : wB;
-        lwt_frag_load(nxt, stream, (i + 1) % (4 * KT), loff);
-        lwt_mma(cur, xf, kc, lane, acc);
-        __builtin_amdgcn_sched_barrier(0);       // one k-tile of weight fragments ahead, not all of them
     }
 }
 

@@ -15,6 +15,7 @@ import torch
 from torch import nn
 
 from ._lib import lib, check, ptr, current_stream, MSMP_ERR_UNSUPPORTED, PackedCache
+from .recurrent import Cell, packed_blob, forward_launch, train_forward, train_backward, _padded_inputs, _state
 
 
 class LEMcuda(nn.Module):
@@ -32,19 +33,8 @@ class LEMcuda(nn.Module):
         self.reset_parameters()
 
     def _pack(self, cache, size_entry, pack_entry):
-        """A blob of the four parameters, `size_entry(ninp, nhid)` floats written by `pack_entry`, cached like LEM._pack (PackedCache)."""
-        ps = [self.weights, self.weights_lin_z, self.bias, self.bias_lin_z]
-
-        def build():
-            L = lib()
-            n_floats = getattr(L, size_entry)(self.ninp, self.nhid)
-            if n_floats <= 0:
-                check(MSMP_ERR_UNSUPPORTED, size_entry)
-            blob = torch.empty(n_floats, dtype=torch.float32, device=ps[0].device)
-            f = [p.detach().to(torch.float32).contiguous() for p in ps]
-            check(getattr(L, pack_entry)(*[ptr(t) for t in f], self.ninp, self.nhid, ptr(blob), current_stream()), pack_entry)
-            return blob
-        return cache.get(ps, build)
+        """A blob of the four parameters, cached like LEM._pack (PackedCache)."""
+        return packed_blob(cache, [self.weights, self.weights_lin_z, self.bias, self.bias_lin_z], size_entry, pack_entry, self.ninp, self.nhid)
 
     def _pack_wide(self):
         """The blob of msmp_lem_encoder_wide_f32 (fp16-split fragments)."""
@@ -116,73 +106,30 @@ class LEMcuda(nn.Module):
         return (y, z) if return_state else y
 
 
-def _padded_inputs(xin):
-    """xin [N, T, ninp] -> float32, rows zero-padded to msmp_lem_input_stride(ninp), contiguous."""
-    ninp = xin.shape[2]
-    stride = lib().msmp_lem_input_stride(ninp)
-    x = xin.detach().to(torch.float32)
-    return (torch.nn.functional.pad(x, (0, stride - ninp)) if stride != ninp else x).contiguous()
-
-
-def _state(t):
-    return None if t is None else t.detach().to(torch.float32).contiguous()
-
-
 def _train_forward(rnn, x, y0, z0, saved=None):
-    """msmp_lem_train_fwd_wide_f32: the fp32-exact recurrence at any width from the states (y0, z0) (None = zeros) -> (y_T, z_T); `saved`: the
-    planes the backward reads (msmp_lem_wide_saved_floats), or None when no backward follows."""
-    n, t_len = x.shape[0], x.shape[1]
-    out = torch.empty(n, rnn.nhid, dtype=torch.float32, device=x.device)
-    z_out = torch.empty_like(out)
-    check(lib().msmp_lem_train_fwd_wide_f32(ptr(x), n, t_len, rnn.ninp, rnn.nhid, rnn.dt, ptr(rnn._pack_wide_train()), ptr(y0), ptr(z0),
-                                            ptr(saved), ptr(out), ptr(z_out), current_stream()), 'msmp_lem_train_fwd_wide_f32')
-    return out, z_out
+    """msmp_lem_train_fwd_wide_f32: the fp32-exact recurrence at any width (recurrent.forward_launch)."""
+    return forward_launch('msmp_lem_train_fwd_wide_f32', x, rnn.ninp, rnn.nhid, (rnn.dt,), rnn._pack_wide_train, y0, z0, saved)
+
+
+# saved planes a2, c, a1, d, y_{t-1}, z'; dG gates g1, g2, g3 (rows of `weights` / `bias`, against [y_{t-1} ; x_t]) and lin (`weights_lin_z` /
+# `bias_lin_z`, against [z' ; x_t])
+_CELL = Cell('msmp_lem_wide_saved_floats', 'msmp_packed_lem_wide_bwd_floats', 'msmp_pack_lem_wide_bwd_f32', 'msmp_lem_train_bwd_wide_f32',
+             n_states=2, gate_planes=(4, 4, 4, 5),
+             grads=lambda rows, w, nh: (None, None, rows(0, (0, 1, 2)).to(w[0].dtype), rows(0, (3,)).to(w[1].dtype), rows(1, (0, 1, 2)),
+                                        rows(1, (3,)), None, None))
 
 
 class _LEMTrainFunction(torch.autograd.Function):
     """LEMFunction of the reference (experiments/models_gnn.py:285-302) on the HIP training kernels at any hidden width 1..256: forward =
-    msmp_lem_train_fwd_wide_f32 (saves the per-step activations), backward = msmp_lem_train_bwd_wide_f32 (BPTT, one launch) followed by ONE
-    msmp_grad_weights_cat_f32 call whose jobs are the 128-column blocks of the four gates of dG (at most 8).  Allocates through torch only and
-    never synchronises (hipGraph capture).  Like the reference it returns no gradient for the step inputs, nor for the initial states."""
+    msmp_lem_train_fwd_wide_f32 (saves the per-step activations), backward = msmp_lem_train_bwd_wide_f32 + the weight-gradient jobs
+    (recurrent.py).  Like the reference it returns no gradient for the step inputs, nor for the initial states."""
 
     @staticmethod
     def forward(ctx, rnn, xin, weights, weights_lin_z, bias, bias_lin_z, y0=None, z0=None):
-        x = _padded_inputs(xin)
-        n, t_len, _ = xin.shape
-        saved = torch.empty(lib().msmp_lem_wide_saved_floats(n, t_len, rnn.nhid), dtype=torch.float32, device=x.device)
-        y0, z0 = _state(y0), _state(z0)
-        out, z_out = _train_forward(rnn, x, y0, z0, saved)
-        ctx.save_for_backward(x, saved, weights, weights_lin_z, *([y0, z0] if y0 is not None else []))
-        ctx.dt, ctx.ninp = rnn.dt, rnn.ninp
-        ctx.mark_non_differentiable(z_out)          # the carried state: a constant for the next call (models_gnn.py:350-353)
-        return out, z_out
+        return train_forward(ctx, _CELL, lambda x, y0, z0, saved: _train_forward(rnn, x, y0, z0, saved), rnn.ninp, rnn.nhid, xin,
+                             (weights, weights_lin_z), y0, z0, (rnn.dt,))
 
-    @staticmethod
-    def backward(ctx, grad_y, _grad_z=None):
-        L = lib()
-        x, saved, weights, weights_lin_z, *states = ctx.saved_tensors
-        y0, z0 = states if states else (None, None)
-        n, t_len, stride = x.shape
-        nh, ninp = weights_lin_z.shape[0], ctx.ninp
-        wp, ldg, nblk = 32 * ((nh + 31) // 32), 128 * ((nh + 127) // 128), (nh + 127) // 128
-        blob = torch.empty(L.msmp_packed_lem_wide_bwd_floats(ninp, nh), dtype=torch.float32, device=x.device)
-        w, wz = (p.detach().to(torch.float32).contiguous() for p in (weights, weights_lin_z))
-        check(L.msmp_pack_lem_wide_bwd_f32(ptr(w), ptr(wz), ninp, nh, ptr(blob), current_stream()), 'msmp_pack_lem_wide_bwd_f32')
-        dg = torch.empty(n * t_len, 4 * ldg, dtype=torch.float32, device=x.device)      # every element is written by the kernel
-        g = grad_y.to(torch.float32).contiguous()
-        check(L.msmp_lem_train_bwd_wide_f32(ptr(g), ptr(saved), ptr(y0), ptr(z0), n, t_len, nh, ctx.dt, ptr(blob), ptr(dg), current_stream()),
-              'msmp_lem_train_bwd_wide_f32')
-        planes = saved.view(6, n * t_len, wp)
-        xs = x.view(n * t_len, stride)[:, :ninp]
-        y_prev, z_new = planes[4][:, :nh], planes[5][:, :nh]        # the forward saves y_{t-1} (y0 at t = 0): the rows of [y_{t-1} ; x_t]
-        from .autograd import grad_weights          # weight / bias gradients: sums over the N*T rows; [state | x_t] is never materialised
-        jobs = [(dg[:, gate * ldg + 128 * j:gate * ldg + 128 * (j + 1)], z_new if gate == 3 else y_prev, xs) for gate in range(4) for j in range(nblk)]
-        r = grad_weights(jobs)
-
-        def rows(kind, gates):          # kind 0: weight, 1: bias blocks of `gates`, without the rows >= width of a last block (zero columns of dG)
-            blocks = [r[2 * (nblk * gate + j) + kind][:min(128, nh - 128 * j)] for gate in gates for j in range(nblk)]
-            return blocks[0] if len(blocks) == 1 else torch.cat(blocks, 0)
-        return (None, None, rows(0, (0, 1, 2)).to(weights.dtype), rows(0, (3,)).to(weights_lin_z.dtype), rows(1, (0, 1, 2)), rows(1, (3,)), None, None)
+    backward = staticmethod(train_backward)
 
 
 _LEMWideTrainFunction = _LEMTrainFunction       # its name while a 128-wide Function stood beside it: the test suite of that revision, run against this library, imports it
