@@ -52,12 +52,12 @@ extern "C" {
 
 typedef void* msmp_stream_t;
 
-/* ABI version: 450 = msmp_g2_gate_blend_f32, msmp_g2_gate_blend_bwd_workspace_bytes, msmp_g2_gate_blend_bwd_f32 and the switch "g2_gate" added; 440 = the eight msmp_*lstm* entries and the switch "lstm_train" added; 430 = the six msmp_*mlp_train* entries and the switch "mlp_train" added; 420 = the five entries of the 128-wide LEM training pair removed (msmp_lem_train_fwd_wide_f32 / _bwd_wide_f32 serve every
+/* ABI version: 460 = msmp_grads_finite_workspace_bytes, msmp_grads_finite_f32, msmp_adamw_guarded_f32 and msmp_status_poison_f32 added; 450 = msmp_g2_gate_blend_f32, msmp_g2_gate_blend_bwd_workspace_bytes, msmp_g2_gate_blend_bwd_f32 and the switch "g2_gate" added; 440 = the eight msmp_*lstm* entries and the switch "lstm_train" added; 430 = the six msmp_*mlp_train* entries and the switch "mlp_train" added; 420 = the five entries of the 128-wide LEM training pair removed (msmp_lem_train_fwd_wide_f32 / _bwd_wide_f32 serve every
  * width) and the blob of msmp_pack_lem_f32 without its last section, which only that pair read; 410 = msmp_mp_layer_decode_f32 and msmp_decoder_t removed;
  * 400 = round 4 (msmp_tiles_t: listed, period_tiles, period_nodes; msmp_build_tiles writes 3 statistics);
  * 300 = round 3 (msmp_last_status, msmp_tiles_t checked on every entry point that takes one).  Bumped whenever a
  * prototype or a blob layout changes; the ctypes host refuses a library whose version is not the one it was written for. */
-#define MSMP_ABI_VERSION 450
+#define MSMP_ABI_VERSION 460
 int msmp_version(void);
 const char* msmp_last_error(void);
 
@@ -513,6 +513,38 @@ int msmp_adamw_f32(int n_tensors, float* const* params, const float* const* grad
 int msmp_adamw_capturable_f32(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
                               float* const* exp_avg_sq, const int64_t* numel, const float* lr_dev, float beta1, float beta2,
                               float eps, float weight_decay, int64_t* step_dev, msmp_stream_t stream);
+
+/* verdict bits of msmp_grads_finite_f32 */
+#define MSMP_NONFINITE_GRAD   1   /* a gradient element is NaN or +-Inf */
+#define MSMP_NONFINITE_SCALAR 2   /* a watched scalar is NaN or +-Inf */
+/* The guard of a training step.  The reference's loop (experiments/train_helper.py:125-141, optimizer of experiments/train.py:410) has none
+ * and needs none: its model has no input range.  Here a forward that leaves the range of the fp16-split path, or a NaN in a label, gives
+ * a non-finite loss, and AdamW would write the non-finite gradients into every weight and both moments.  The three entries below
+ * refuse such an update on the device: no atomics, no memset, no host read-back, so a captured (hipGraph) step stays a graph.
+ * All three return MSMP_ERR_ARG for a null pointer or a bad count before anything is launched.
+ *
+ * msmp_grads_finite_f32: verdict_dev[0] (int32, overwritten by every call) = 0 if every element of the n_tensors gradient tensors
+ * (device pointers and host element counts as msmp_adamw_f32; 48 descriptors per launch, 4096 elements per block) and every one of the
+ * n_scalars (0 .. 4) single-float device scalars (the loss) is finite, else MSMP_NONFINITE_GRAD | MSMP_NONFINITE_SCALAR as they apply.
+ * NaN and +-Inf are not finite; FLT_MAX, denormals and zeros are.  The pointer of a tensor
+ * of 0 elements is not read and may be NULL.  Two launches per call (one more per further 48 tensors): every block
+ * overwrites its own word of workspace (>= msmp_grads_finite_workspace_bytes(n_tensors, numel) bytes, else MSMP_ERR_WORKSPACE; the query
+ * returns 0 for arguments the entry refuses), the final block overwrites the verdict. */
+size_t msmp_grads_finite_workspace_bytes(int n_tensors, const int64_t* numel);
+int msmp_grads_finite_f32(int n_tensors, const float* const* grads, const int64_t* numel, int n_scalars, const float* const* scalars,
+                          int32_t* verdict_dev, void* workspace, size_t workspace_bytes, msmp_stream_t stream);
+/* msmp_adamw_capturable_f32 (experiments/train.py:410) behind that verdict: with verdict_dev[0] == 0 the same launches on the same
+ * arithmetic (bit for bit, step_dev advanced by one); with any other value no parameter, moment or step_dev byte changes and
+ * skipped_dev[0] (int64) advances by one. */
+int msmp_adamw_guarded_f32(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
+                           float* const* exp_avg_sq, const int64_t* numel, const float* lr_dev, float beta1, float beta2,
+                           float eps, float weight_decay, int64_t* step_dev, const int32_t* verdict_dev, int64_t* skipped_dev,
+                           msmp_stream_t stream);
+/* The sticky range status (msmp_last_status) as a value in the stream: if the word is not 0 when this one-wave kernel runs, scalar[0]
+ * becomes a quiet NaN (the loss sum of experiments/train_helper.py:125-141, before the data-parallel all-reduce: every rank then takes the
+ * same decision).  The word is read with a system-scope atomic load; the kernels that raise it do so with system-scope atomic ORs, so
+ * stream order is enough.  Without a status word (its allocation failed) nothing is launched. */
+int msmp_status_poison_f32(float* scalar, msmp_stream_t stream);
 
 /* Deterministic reductions for the PyTorch-side pieces of a training iteration (bias gradients of the encoder / decoder, the
  * loss of experiments/train_helper.py:125-141): fixed summation order, two kernel launches, no atomics, no memset -- safe inside a

@@ -6,11 +6,36 @@ The loss is sqrt(S) with S = sum over ALL nodes of the batch, which is not a mea
 exact data parallelism is:  (1) all-reduce(SUM) the scalar S_k of every rank;  (2) backward S_k scaled by
 1/(2 sqrt(S));  (3) all-reduce(SUM) the gradients (one flat ~5 MB buffer: 1.25-1.34 M fp32 parameters),
 RCCL over xGMI when the backend is nccl.  Parameters are replicated; every rank must draw the same
-`unrolled_graphs` and its own slice of `random_steps`."""
+`unrolled_graphs` and its own slice of `random_steps`.
+
+Range policy of the optimisation step (`range_policy` of CapturedTrainStep and training_step; optim.AdamW(skip_nonfinite=True)).
+The default (fp16-split) matrix path carries node rows with |x| <= 255 and activations with |x| <= 1023; the reference has no such
+limit (models_gnn.py:1315-1377) and its loop (experiments/train_helper.py:125-141) simply trains on such data.  Solver.forward
+handles the limit for inference (Solver.range_policy); the same semantics for training:
+    None     no check: what the step did before the policy existed.
+    'auto'   the FIRST call of a capture (the first eager step of a model) is followed by one stream synchronisation and a read of
+             the sticky status word (msmp_last_status): if a kernel left the range, the model switches to the exact-fp32 kernels,
+             with one MsmpRangeWarning, and THAT step is evaluated again on them (the device had skipped it: see below), so it is
+             not dropped.  Later calls read the word at entry without a synchronisation (flags raised by work that has completed
+             since): same switch from that call on; the steps in between were skipped on the device, are dropped, and the warning
+             counts them.
+    'sync'   every call is checked like the first one: no step is ever dropped and the trajectory is the reference's (one stream
+             synchronisation per step).
+What keeps a step that left the range from reaching the weights is on the device: msmp_status_poison_f32 turns a raised status word
+into a NaN in this rank's S_k before the scalar all-reduce (so every rank sees a NaN loss), and the optimizer's finite check +
+guarded AdamW (skip_nonfinite) then skips the update on every rank alike.  A NaN or Inf that comes from the data (a NaN in a label)
+is skipped the same way; it raises no range status and switches nothing."""
+import os
+import warnings
+
 import torch
 import torch.distributed as dist
 
+from . import _lib
 from .reductions import sqerr_sum
+
+_POLICIES = (None, 'auto', 'sync')
+_SWITCHED = 1 << 30           # beside the MSMP_STATUS_* bits: the model was switched to the exact-fp32 kernels by somebody else
 
 
 def _world():
@@ -33,11 +58,85 @@ def allreduce_gradients(params):
         off += n
 
 
-def dp_loss_backward(model, graph):
+def _check_policy(policy, optimizer):
+    if policy not in _POLICIES:
+        raise ValueError(f"range_policy must be None, 'auto' or 'sync', not {policy!r}")
+    if policy is not None and not getattr(optimizer, 'skip_nonfinite', False):
+        raise ValueError(f'range_policy={policy!r} needs msmp_pde_amd.optim.AdamW(..., capturable=True, skip_nonfinite=True): '
+                         'the step that left the range is skipped on the device')
+
+
+def _range_flags(model, exact, device):
+    """What the policy acts on: the sticky status word (unless this step already runs on the exact-fp32 kernels, which have no range
+    to leave), plus _SWITCHED if the model was switched while this step was not.  One host read, no synchronisation -- except under
+    data parallelism, where the ranks must act together (a new capture's warm-up and a repeated step run collectives): one 4-byte
+    all-reduce(MAX) makes the value common."""
+    flags = 0 if exact else _lib.last_status()
+    if getattr(model, '_range_exact', False) and not exact:
+        flags |= _SWITCHED
+    if _world() > 1:
+        t = torch.tensor([flags], dtype=torch.int32, device=device)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        flags = int(t.item())
+    return flags
+
+
+def _new_skips(optimizer):
+    """Steps the optimizer's guard skipped since the last call of this function (a host read: synchronises)."""
+    total = optimizer.skipped_steps
+    new = total - getattr(optimizer, '_msmp_skips_reported', 0)
+    optimizer._msmp_skips_reported = total
+    return new
+
+
+def _range_recover(model, optimizer, flags, repeated):
+    """The switch of Solver._range_switch for a training step: the model runs on the exact-fp32 kernels from now on, one
+    MsmpRangeWarning says how many optimisation steps were dropped, the status word is cleared."""
+    skipped = _new_skips(optimizer)                         # synchronises: the work that raised the word has completed
+    dropped = max(skipped - (1 if repeated else 0), 0)
+    model._range_exact = True
+    status = flags & ~_SWITCHED
+    what = ('the fp16-split matrix path left its range during training: ' + '; '.join(t for b, t in _lib._STATUS_TEXT.items() if status & b)
+            if status else 'the model was switched to the exact-fp32 kernels outside the training step')
+    msg = (f'msmp_pde_amd: {type(model).__name__}: {what}.  {dropped} optimisation step(s) were dropped (skipped on the device before the '
+           'host saw the flag)' + ('; the step that raised it is evaluated again' if repeated else '') + '.  The model and its training step now '
+           'run on the exact-fp32 MFMA kernels (no range limit, about 2x slower).  Rescale the data to keep the fast path.')
+    _lib.last_status(reset=True)
+    if os.environ.get('MSMP_STRICT_RANGE') == '1':
+        raise _lib.MsmpError(msg)
+    warnings.warn(msg, _lib.MsmpRangeWarning, stacklevel=4)
+    return dropped
+
+
+def _status_poison(s_local):
+    """S_k behind msmp_status_poison_f32: NaN if the sticky status word is raised when the kernel runs, else unchanged.  The float32
+    scalar of the library's loss sum is poisoned in place (one one-wave launch); any other dtype (float64 inputs keep PyTorch's sum)
+    gets a float32 zero that went through the kernel added to it."""
+    if not s_local.is_cuda:
+        return s_local
+    if s_local.dtype == torch.float32 and s_local.numel() == 1 and s_local.is_contiguous():
+        _lib.check(_lib.lib().msmp_status_poison_f32(s_local.data_ptr(), _lib.current_stream()), 'msmp_status_poison_f32')
+        return s_local
+    flag = torch.empty(1, dtype=torch.float32, device=s_local.device).fill_(0.0)
+    _lib.check(_lib.lib().msmp_status_poison_f32(flag.data_ptr(), _lib.current_stream()), 'msmp_status_poison_f32')
+    return s_local + flag.to(s_local.dtype).view(s_local.shape)
+
+
+def _watchable(loss):
+    """The float32 scalar the optimizer's finite check reads for `loss` (made where the loss is made: a capture replays it)."""
+    return loss if loss.dtype == torch.float32 else loss.detach().float()
+
+
+def dp_loss_backward(model, graph, range_guard=False):
     """Forward + backward of the reference's loss on this rank's shard; gradients are left all-reduced
-    (identical on every rank and equal to the single-device gradient).  Returns the global loss sqrt(S)."""
+    (identical on every rank and equal to the single-device gradient).  Returns the global loss sqrt(S).
+    range_guard: this rank's S_k passes through msmp_status_poison_f32 before the scalar all-reduce: if a kernel of ANY forward so
+    far left the range of the fp16-split path (the sticky status word is raised), S, the loss RETURNED (NaN) and every rank's
+    gradients are not finite, and optim.AdamW(skip_nonfinite=True) skips the update on every rank with no further collective."""
     pred = model(graph)
     s_local = sqerr_sum(pred, graph.y)                      # MSELoss(reduction='sum'), deterministic two-launch kernel on the GPU
+    if range_guard:
+        s_local = _status_poison(s_local)
     s_total = s_local.detach().clone()
     if _world() > 0:
         dist.all_reduce(s_total, op=dist.ReduceOp.SUM)
@@ -47,12 +146,55 @@ def dp_loss_backward(model, graph):
     return loss
 
 
-def training_step(model, creator, u_super, x, variables, random_steps, unrolled_graphs, optimizer, captured=None):
+def _guarded_eager_step(model, graph, optimizer, policy):
+    """`dp_loss_backward` + `optimizer.step()` under a range policy (see the module docstring): the rules of CapturedTrainStep without
+    a capture."""
+    def once():
+        optimizer.zero_grad()
+        loss = dp_loss_backward(model, graph, range_guard=not getattr(model, '_range_exact', False))
+        watched = _watchable(loss)
+        optimizer.watch(watched)
+        try:
+            optimizer.step()
+        finally:
+            optimizer.unwatch(watched)
+        return loss
+    dev = graph.x.device
+    dp = _world() > 1               # the ranks read the flags together, whatever kernels each of them is on (see _range_flags)
+    exact = lambda: bool(getattr(model, '_range_exact', False))
+    if dp or not exact():
+        flags = _range_flags(model, exact(), dev)
+        if flags and not exact():
+            _range_recover(model, optimizer, flags, repeated=False)
+    probe = (dp or not exact()) and (policy == 'sync' or not getattr(model, '_range_probed_train', False))
+    loss = once()
+    if probe:
+        model._range_probed_train = True
+        torch.cuda.current_stream().synchronize()
+        flags = _range_flags(model, exact(), dev)
+        if flags:
+            repeat = optimizer.last_step_skipped            # the same on every rank: gradients and loss are all-reduced
+            if not exact():
+                _range_recover(model, optimizer, flags, repeated=repeat)
+            if repeat:
+                loss = once()
+    return loss
+
+
+def training_step(model, creator, u_super, x, variables, random_steps, unrolled_graphs, optimizer, captured=None, range_policy=None):
     """One iteration of training_loop (experiments/train_helper.py:91-141) on this rank's samples.
     captured: a CapturedTrainStep built on a batch of the same structure (same grid, batch size and neighbourhood): forward + loss +
-    backward + optimizer update are then ONE hipGraph launch; the pushforward unrolling stays eager (inference kernels)."""
+    backward + optimizer update are then ONE hipGraph launch; the pushforward unrolling stays eager (inference kernels).
+    range_policy: None, 'auto' or 'sync' (module docstring); handed to `captured` (it replaces the policy the step was built with),
+    or applied around the eager `dp_loss_backward` + `optimizer.step()`.  The loss returned for a step the guard skipped is NaN."""
+    _check_policy(range_policy, optimizer)
     if captured is None:
         optimizer.zero_grad()
+    elif range_policy is not None:
+        if captured.range_policy is None:
+            raise ValueError('training_step(range_policy=...): `captured` was built without one (its graph holds no status poison); '
+                             'build it with CapturedTrainStep(..., range_policy=...)')
+        captured.range_policy = range_policy
     steps = list(random_steps)
     data, labels = creator.create_data(u_super, steps)
     graph = creator.create_graph(data, labels, x, variables, steps)
@@ -64,6 +206,8 @@ def training_step(model, creator, u_super, x, variables, random_steps, unrolled_
             graph = creator.create_next_graph(graph, pred, labels, steps)
     if captured is not None:
         loss = captured(graph)
+    elif range_policy is not None:
+        loss = _guarded_eager_step(model, graph, optimizer, range_policy)
     else:
         loss = dp_loss_backward(model, graph)
         optimizer.step()
@@ -101,22 +245,53 @@ class CapturedTrainStep:
         graph F: forward + this rank's S_k;   all-reduce(SUM) of the scalar S;
         graph B: loss = sqrt(S), backward of S_k / (2 loss);   ONE flat all-reduce(SUM) of the gradients (RCCL over xGMI);
         graph U: the AdamW update.
-    Without a process group (or with a one-rank group) it is ONE graph."""
+    Without a process group (or with a one-rank group) it is ONE graph.
 
-    def __init__(self, model, optimizer, graph, warmup=3):
+    range_policy: None (no check), 'auto' or 'sync' -- the module docstring; both need optim.AdamW(skip_nonfinite=True).  The capture
+    then holds the status poison behind the loss sum (graph F) and the finite check + guarded AdamW as its update (graph U), with the
+    captured loss registered through `optimizer.watch`.  Recovering means capturing again with the forward on the exact-fp32
+    kernels (`_exact`); building a capture does not train, so neither does that.  `skipped_steps` (the optimizer's count: steps the
+    device skipped, a repeated one included) and `dropped_steps` (those never repeated) are kept; the loss returned for a skipped
+    step is NaN."""
+
+    def __init__(self, model, optimizer, graph, warmup=3, range_policy=None):
         import copy
-        from . import autograd as _ag
-        from ._lib import invalidate_packed_weights, cached_operands, _Workspace
+        from ._lib import invalidate_packed_weights
         if not all(g.get('capturable') for g in optimizer.param_groups):
             raise RuntimeError('CapturedTrainStep needs msmp_pde_amd.optim.AdamW(..., capturable=True)')
+        _check_policy(range_policy, optimizer)
         self.model, self.opt = model, optimizer
+        self.range_policy = range_policy
+        self.dropped_steps = 0
+        self._warmup = warmup
+        self._probed = False          # the synchronous first-call check has been done
+        self.loss = self._watched = None
         self.data = copy.copy(graph)
         self._float_keys = [k for k in graph.keys() if torch.is_tensor(getattr(graph, k)) and getattr(graph, k).is_floating_point()]
         for k in self._float_keys:
             setattr(self.data, k, getattr(graph, k).clone())
-        dev = self.data.x.device
         self._invalidate = invalidate_packed_weights
         self._dp = _world() > 1
+        self._capture()
+
+    @property
+    def skipped_steps(self):
+        """Optimisation steps the guard skipped on the device (optimizer.skipped_steps: a host read, synchronises)."""
+        return self.opt.skipped_steps
+
+    def _capture(self):
+        """Warm-up and capture on the batch in the static tensors; the forward runs on the kernels the model is on now."""
+        from . import autograd as _ag
+        from ._lib import invalidate_packed_weights, cached_operands, _Workspace
+        model, optimizer, warmup = self.model, self.opt, self._warmup
+        guarded = bool(getattr(optimizer, 'skip_nonfinite', False))
+        if self._watched is not None:
+            optimizer.unwatch(self._watched)              # the previous capture's scalar lives in the pool of the graphs dropped here
+            self._watched = None
+        self.graph = self._graphs = None
+        self._exact = bool(getattr(model, '_range_exact', False))       # Solver.forward puts the forward under _lib.exact_fp32() then
+        poison = self.range_policy is not None and not self._exact     # the exact-fp32 kernels have no range to leave
+        dev = self.data.x.device
         params = list(model.parameters())
         old_bwd = _ag._bwd_ws.pop(dev, None)              # the backward's grow-only scratch: a private one for the graph
         try:
@@ -133,10 +308,11 @@ class CapturedTrainStep:
                     ts = [int(optimizer.state[p]['step'].item()) for p in g['params'] if optimizer.state.get(p)]
                     return ts[0] if ts else 0
                 d0 = [_count(g) for g in optimizer.param_groups]
+                k0 = [int(g['_msmp_dev']['skipped'].item()) if g.get('_msmp_dev') and 'skipped' in g['_msmp_dev'] else 0 for g in optimizer.param_groups]
                 with torch.cuda.stream(side):             # eager warm-up: optimizer state, workspaces, structure caches
                     for _ in range(warmup):
                         optimizer.zero_grad(set_to_none=True)
-                        dp_loss_backward(model, self.data)
+                        dp_loss_backward(model, self.data, range_guard=poison)
                         optimizer.step()
                 torch.cuda.current_stream().wait_stream(side)
                 torch.cuda.synchronize()
@@ -150,15 +326,20 @@ class CapturedTrainStep:
                         for k, v in st.items():
                             if torch.is_tensor(v):
                                 v.copy_(s0[id(p)][k]) if had_state[id(p)] else v.zero_()
-                    for g, d in zip(optimizer.param_groups, d0):
+                    for g, d, k in zip(optimizer.param_groups, d0, k0):
                         if g.get('_msmp_dev'):
                             g['_msmp_dev']['step'].fill_(d)
+                            if 'skipped' in g['_msmp_dev']:
+                                g['_msmp_dev']['skipped'].fill_(k)
                 optimizer.zero_grad(set_to_none=True)
                 invalidate_packed_weights()               # the pack kernels must be part of the graph
                 if not self._dp:
                     self.graph = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(self.graph):
-                        self.loss = dp_loss_backward(model, self.data)
+                        self.loss = dp_loss_backward(model, self.data, range_guard=poison)
+                        if guarded:
+                            self._watched = _watchable(self.loss)
+                            optimizer.watch(self._watched)
                         optimizer.step()
                     self._graphs = [self.graph]
                 else:
@@ -167,10 +348,16 @@ class CapturedTrainStep:
                     with torch.cuda.graph(gf, stream=cap):
                         pred = model(self.data)
                         self._s_local = sqerr_sum(pred, self.data.y)
+                        if poison:
+                            self._s_local = _status_poison(self._s_local)
                     self._s_total = self._s_local.detach().clone()
                     with torch.cuda.graph(gb, pool=gf.pool(), stream=cap):
                         self.loss = torch.sqrt(self._s_total)
                         (self._s_local / (2.0 * self.loss)).backward()
+                        if guarded:
+                            self._watched = _watchable(self.loss)
+                    if guarded:
+                        optimizer.watch(self._watched)
                     with torch.cuda.graph(gu, pool=gf.pool(), stream=cap):
                         optimizer.step()
                     self._graphs = [gf, gb, gu]
@@ -202,11 +389,36 @@ class CapturedTrainStep:
             if not st or st['exp_avg'] is not m or st['exp_avg_sq'] is not v:
                 raise RuntimeError('CapturedTrainStep: the optimizer state tensors were replaced (optimizer.load_state_dict): capture again')
 
+    def _recover(self, flags, repeated):
+        if not self._exact:
+            self.dropped_steps += _range_recover(self.model, self.opt, flags, repeated)
+        self._capture()           # data parallel: by every rank, also one that is on the exact kernels already (the warm-up runs collectives)
+
     def __call__(self, graph):
         self._check_pointers()
+        policy = self.range_policy
+        dev = self.data.x.device
+        if policy is not None and (self._dp or not self._exact):
+            flags = _range_flags(self.model, self._exact, dev)         # raised by replays that have completed since, or a model switched elsewhere
+            if flags:
+                self._recover(flags, repeated=False)
         for k in self._float_keys:
             getattr(self.data, k).copy_(getattr(graph, k))
         self.opt.sync_lr()                                # a scheduler may have changed param_groups[i]["lr"]
+        self._replay()
+        if policy is not None and (self._dp or not self._exact) and (policy == 'sync' or not self._probed):
+            self._probed = True
+            torch.cuda.current_stream().synchronize()
+            flags = _range_flags(self.model, self._exact, dev)
+            if flags:
+                repeat = self.opt.last_step_skipped       # the poison made the device skip this step; the batch is still in the static tensors
+                self._recover(flags, repeated=repeat)
+                if repeat:
+                    self._replay()
+        self._invalidate()
+        return self.loss.clone()
+
+    def _replay(self):
         if not self._dp:
             self.graph.replay()
         else:
@@ -217,5 +429,3 @@ class CapturedTrainStep:
             gb.replay()
             allreduce_gradients([p for p, _ in self._params])
             gu.replay()
-        self._invalidate()
-        return self.loss.clone()
