@@ -52,12 +52,12 @@ extern "C" {
 
 typedef void* msmp_stream_t;
 
-/* ABI version: 460 = msmp_grads_finite_workspace_bytes, msmp_grads_finite_f32, msmp_adamw_guarded_f32 and msmp_status_poison_f32 added; 450 = msmp_g2_gate_blend_f32, msmp_g2_gate_blend_bwd_workspace_bytes, msmp_g2_gate_blend_bwd_f32 and the switch "g2_gate" added; 440 = the eight msmp_*lstm* entries and the switch "lstm_train" added; 430 = the six msmp_*mlp_train* entries and the switch "mlp_train" added; 420 = the five entries of the 128-wide LEM training pair removed (msmp_lem_train_fwd_wide_f32 / _bwd_wide_f32 serve every
+/* ABI version: 470 = msmp_batch_assemble_f32 added; 460 = msmp_grads_finite_workspace_bytes, msmp_grads_finite_f32, msmp_adamw_guarded_f32 and msmp_status_poison_f32 added; 450 = msmp_g2_gate_blend_f32, msmp_g2_gate_blend_bwd_workspace_bytes, msmp_g2_gate_blend_bwd_f32 and the switch "g2_gate" added; 440 = the eight msmp_*lstm* entries and the switch "lstm_train" added; 430 = the six msmp_*mlp_train* entries and the switch "mlp_train" added; 420 = the five entries of the 128-wide LEM training pair removed (msmp_lem_train_fwd_wide_f32 / _bwd_wide_f32 serve every
  * width) and the blob of msmp_pack_lem_f32 without its last section, which only that pair read; 410 = msmp_mp_layer_decode_f32 and msmp_decoder_t removed;
  * 400 = round 4 (msmp_tiles_t: listed, period_tiles, period_nodes; msmp_build_tiles writes 3 statistics);
  * 300 = round 3 (msmp_last_status, msmp_tiles_t checked on every entry point that takes one).  Bumped whenever a
  * prototype or a blob layout changes; the ctypes host refuses a library whose version is not the one it was written for. */
-#define MSMP_ABI_VERSION 460
+#define MSMP_ABI_VERSION 470
 int msmp_version(void);
 const char* msmp_last_error(void);
 
@@ -545,6 +545,29 @@ int msmp_adamw_guarded_f32(int n_tensors, float* const* params, const float* con
  * same decision).  The word is read with a system-scope atomic load; the kernels that raise it do so with system-scope atomic ORs, so
  * stream order is enough.  Without a status word (its allocation failed) nothing is launched. */
 int msmp_status_poison_f32(float* scalar, msmp_stream_t stream);
+
+/* A training batch from a device-resident dataset in ONE launch: GraphCreator.create_data + create_graph (common/utils.py:300-428;
+ * mode 0) or the label / time half of create_next_graph (common/utils.py:431-471, 454-469; mode 1), with the sample and step indices
+ * read on the device (experiments/train_helper.py:94-112 draws them per iteration).
+ *   store      [n_samples, nt, comps, nx] fp32: the downprojected split in the per-sample layout of HDF5Dataset.__getitem__
+ *              (common/utils.py:156-264); comps = 2 for the AD / *2D experiments, else 1;
+ *   sample_idx, steps   [batch] int32 DEVICE arrays;   t_axis [nt], x_grid [nx];   var_table [n_samples, n_vars] (NULL at n_vars = 0).
+ * For graph b with s = sample_idx[b], p = steps[b], node i < nx, component c < comps, k < tw:
+ *   x_out[b nx + i, c tw + k] = store[s, p - tw + k, c, i]      ([batch nx, comps tw], component-major as GraphCreator._flatten, :350-357)
+ *   y_out[b nx + i, c tw + k] = store[s, p + k, c, i]
+ *   pos_out[b nx + i]         = (t_axis[p], x_grid[i])          ([batch nx, 2])
+ *   vars_out[v batch nx + b nx + i] = var_table[s, v]           (n_vars contiguous columns of batch nx floats)
+ * mode 1 writes y_out and column 0 of pos_out only (column 1 keeps its bytes); x_out, x_grid, var_table and vars_out may be NULL.
+ * The indices live on the device, so the entry cannot refuse a bad one; the kernel never reads outside `store`: a graph whose s is
+ * outside 0 .. n_samples - 1 or whose p is outside tw .. nt - tw gets quiet-NaN rows in x_out and y_out (a NaN loss, which
+ * msmp_adamw_guarded_f32 skips), pos / vars rows from t_axis[clamp(p, tw, nt - tw)] and row clamp(s, 0, n_samples - 1), and every
+ * other graph of the batch is unaffected.  Refused by value before anything is launched -- MSMP_ERR_ARG: a null pointer; batch, nx,
+ * nt or n_samples outside 1 .. 2^31 - 1; batch nx >= 2^31; comps not 1 or 2; n_vars outside 0..3; mode not 0 or 1.
+ * MSMP_ERR_UNSUPPORTED: tw outside 1..64, or nt < 2 tw.  No allocation, no synchronisation, no atomics, no memset: only pointers and
+ * sizes are baked into the launch, so a captured one replayed after sample_idx / steps were overwritten assembles the new batch. */
+int msmp_batch_assemble_f32(const float* store, int64_t n_samples, int nt, int comps, int nx, const int32_t* sample_idx,
+                            const int32_t* steps, int batch, int tw, const float* t_axis, const float* x_grid, const float* var_table,
+                            int n_vars, int mode, float* x_out, float* y_out, float* pos_out, float* vars_out, msmp_stream_t stream);
 
 /* Deterministic reductions for the PyTorch-side pieces of a training iteration (bias gradients of the encoder / decoder, the
  * loss of experiments/train_helper.py:125-141): fixed summation order, two kernel launches, no atomics, no memset -- safe inside a

@@ -24,7 +24,7 @@ MSMP_LAYER_LIN = 1
 MSMP_ERR_UNSUPPORTED = -2
 MSMP_MAX_VARS = 8
 HIDDEN = 128
-MSMP_ABI_VERSION = 460          # include/msmp_pde.h: the library must report exactly this
+MSMP_ABI_VERSION = 470          # include/msmp_pde.h: the library must report exactly this
 MSMP_STATUS_INPUT_RANGE, MSMP_STATUS_NODE_SATURATED, MSMP_STATUS_NONFINITE = 1, 2, 4
 
 # name -> (restype, argtypes); must list every symbol include/msmp_pde.h declares
@@ -100,6 +100,8 @@ SIGNATURES = {
     'msmp_adamw_guarded_f32': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_void_p,
                                        c_void_p, c_void_p, c_void_p]),
     'msmp_status_poison_f32': (c_int, [c_void_p, c_void_p]),
+    'msmp_batch_assemble_f32': (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'msmp_reduce_workspace_bytes': (c_size_t, [c_int]),
     'msmp_colsum_f32': (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     'msmp_sqerr_sum_f32': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),

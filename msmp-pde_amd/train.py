@@ -187,14 +187,7 @@ def training_step(model, creator, u_super, x, variables, random_steps, unrolled_
     backward + optimizer update are then ONE hipGraph launch; the pushforward unrolling stays eager (inference kernels).
     range_policy: None, 'auto' or 'sync' (module docstring); handed to `captured` (it replaces the policy the step was built with),
     or applied around the eager `dp_loss_backward` + `optimizer.step()`.  The loss returned for a step the guard skipped is NaN."""
-    _check_policy(range_policy, optimizer)
-    if captured is None:
-        optimizer.zero_grad()
-    elif range_policy is not None:
-        if captured.range_policy is None:
-            raise ValueError('training_step(range_policy=...): `captured` was built without one (its graph holds no status poison); '
-                             'build it with CapturedTrainStep(..., range_policy=...)')
-        captured.range_policy = range_policy
+    _begin_step(optimizer, captured, range_policy)
     steps = list(random_steps)
     data, labels = creator.create_data(u_super, steps)
     graph = creator.create_graph(data, labels, x, variables, steps)
@@ -204,6 +197,23 @@ def training_step(model, creator, u_super, x, variables, random_steps, unrolled_
             _, labels = creator.create_data(u_super, steps)
             pred = model(graph)
             graph = creator.create_next_graph(graph, pred, labels, steps)
+    return _finish_step(model, graph, optimizer, captured, range_policy)
+
+
+def _begin_step(optimizer, captured, range_policy):
+    """What an iteration does before its batch is made: the policy check, and zero_grad (eager) or the policy handed to the capture."""
+    _check_policy(range_policy, optimizer)
+    if captured is None:
+        optimizer.zero_grad()
+    elif range_policy is not None:
+        if captured.range_policy is None:
+            raise ValueError('training_step(range_policy=...): `captured` was built without one (its graph holds no status poison); '
+                             'build it with CapturedTrainStep(..., range_policy=...)')
+        captured.range_policy = range_policy
+
+
+def _finish_step(model, graph, optimizer, captured, range_policy):
+    """Forward, loss, backward and update on the batch `graph` (experiments/train_helper.py:124-145), captured or eager."""
     if captured is not None:
         loss = captured(graph)
     elif range_policy is not None:
@@ -215,6 +225,31 @@ def training_step(model, creator, u_super, x, variables, random_steps, unrolled_
     if hasattr(lem, 'reset_states'):
         lem.reset_states()
     return loss
+
+
+def dataset_training_step(model, creator, dataset, indices, random_steps, unrolled_graphs, optimizer, captured=None, range_policy=None):
+    """`training_step` fed by a data.DeviceDataset: the same iteration (experiments/train_helper.py:91-141) on the samples `indices` of
+    the dataset, with dataset.batch / dataset.advance (one launch each) in place of create_data / create_graph / create_next_graph.
+    indices / random_steps: lists (range-checked on the host) or device int tensors.
+    captured: a CapturedTrainStep built on a batch of this dataset (float32 tensors of the same batch size).  Without unrolling the
+    batch is assembled straight into its static tensors (`captured.data`) and replayed: its copies of a tensor onto itself are no-ops.
+    With unrolling, as in the eager case, the batch is assembled into a working Data the dataset reuses (create_next_graph rebinds
+    graph.x to the prediction, which must not happen to the capture's static tensors) and `captured` copies it in.
+    range_policy: as in `training_step`."""
+    import copy
+    _begin_step(optimizer, captured, range_policy)
+    tensors = torch.is_tensor(random_steps)
+    steps = random_steps if tensors else list(random_steps)
+    if captured is not None and unrolled_graphs == 0:
+        graph = dataset.batch(creator, indices, steps, out=captured.data)
+    else:
+        graph = copy.copy(dataset.working_batch(creator, indices, steps))     # a shallow copy: rebinding graph.x leaves the working Data whole
+        with torch.no_grad():                               # pushforward trick, :106-112
+            for _ in range(unrolled_graphs):
+                steps = steps + creator.tw if tensors else [s + creator.tw for s in steps]
+                pred = model(graph)
+                graph = dataset.advance(graph, pred, indices, steps)
+    return _finish_step(model, graph, optimizer, captured, range_policy)
 
 
 class CapturedTrainStep:
