@@ -2,10 +2,10 @@
 
 Forward values always come from the HIP kernels (msmp_mp_layer_f32); only the layer's inputs are saved.  The backward
 pass RECOMPUTES the layer in materialised form and differentiates it with explicit formulas, all of it behind ONE C-ABI call
-per layer / gated pair (msmp_mp_layer_bwd_f32, train_kernels.hip): GEMMs with edge- / node-sized outputs on the library's own
-bf16x3 row-GEMM kernels (rocblas_sgemm only with msmp_tune("bwd_gemm", 0), for A/B runs), everything
+per layer / gated pair (msmp_mp_layer_bwd_f32, layer_bwd_kernel.hip): GEMMs with edge- / node-sized outputs on the library's own
+bf16x3 row-GEMM kernels (rows_gemm_kernel.hip; rocblas_sgemm only with msmp_tune("bwd_gemm", 0), for A/B runs), everything
 else HIP kernels too (edge concat, bias + Swish, mean-backward + Swish', InstanceNorm backward, gated-blend backward, scatters,
-the batched weight-gradient kernel).  `EXPLICIT_BACKWARD = 1` runs the same algorithm orchestrated from Python (library GEMMs
+the batched weight-gradient kernel of grad_weights_kernel.hip).  `EXPLICIT_BACKWARD = 1` runs the same algorithm orchestrated from Python (library GEMMs
 through torch, ~65 ops per pair), `0` differentiates a PyTorch restatement with torch.autograd (~190 ops): kept for cross-checks.  Nothing runs on
 the CPU and nothing here is used by the inference / rollout path.  The math is that of experiments/models_gnn.py:61-149
 and :1204-1207.  At a hidden width other than 128 (the GLU classes: 164) the backward is msmp_wide_layer_bwd_f32

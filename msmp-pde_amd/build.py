@@ -28,7 +28,10 @@ SOURCES = {  # file -> extra flags
     'wide_message_kernel.hip': [],
     'wide_node_tail_kernel.hip': [],
     'wide_node_proj_kernel.hip': [],
-    'train_kernels.hip': [],
+    'rows_gemm_kernel.hip': [],
+    'grad_weights_kernel.hip': [],
+    'layer_bwd_kernel.hip': [],
+    'optim_kernels.hip': [],
     'mlp2_kernel.hip': [],
     'wide_kernels.hip': [],
     'wide_layer_bwd_kernel.hip': [],

@@ -20,7 +20,6 @@
 // no cross-lane step, no LDS, no atomic and no memset, and the summation order is the list's: two runs give the same bits.  Plain fp32:
 // no input range, the range status is neither read nor raised.  tau is saved by the forward for the backward (one [N, ld] tensor).
 #include "msmp_common.h"
-#include "train_internal.h"
 
 namespace msmp {
 

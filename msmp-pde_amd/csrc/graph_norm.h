@@ -1,4 +1,4 @@
-// Per-graph column statistics shared by the InstanceNorm kernels (aux_kernels.hip) and their backward (train_kernels.hip).
+// Per-graph column statistics shared by the InstanceNorm kernels (aux_kernels.hip) and their backward (layer_bwd_kernel.hip).
 // One 256-thread workgroup per graph: thread = (16-B channel group cg = tid & 31, row slice rs = tid >> 5).
 #pragma once
 #include "msmp_common.h"

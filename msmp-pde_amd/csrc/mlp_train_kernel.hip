@@ -29,8 +29,8 @@
 //   dz1    [N][ldz1]                ldz1 = 128 ceil(heads W / 128): head h at columns h W ..; columns heads W .. ldz1 - 1 are written as 0
 //   dz2, a1 [N][ldz]                ldz = 128 ceil(W / 128), likewise (two-layer form only)
 // which is what a weight-gradient job reads: A = 128 columns of dz (row stride ldz), B = a1 or x.
+#include "grad_weights.h"
 #include "train_frags.h"
-#include "train_internal.h"
 
 namespace msmp {
 

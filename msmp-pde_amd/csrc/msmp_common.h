@@ -99,6 +99,10 @@ __device__ __forceinline__ float sigmoidf_(float x) {
     return __builtin_amdgcn_rcpf(1.0f + e);
 }
 #endif
+__device__ __forceinline__ float dswish(float x) {        // d/dx x sigmoid(x)
+    const float s = sigmoidf_(x);
+    return s * (1.0f + x * (1.0f - s));
+}
 
 // Row of a 32x32 MFMA accumulator register: D[row][col = lane & 31].
 __device__ __forceinline__ int acc_row(int reg, int hh) { return (reg & 3) + 8 * (reg >> 2) + 4 * hh; }
@@ -116,6 +120,10 @@ int* status_ptr();          // aux_kernels.hip: the status word as the device se
 
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
+inline unsigned grid_for(long work_items) {      // workgroups of 256 threads for a grid-stride kernel: 1 .. 32 768
+    const long b = (work_items + 255) / 256;
+    return (unsigned)(b < 1 ? 1 : b > 32768 ? 32768 : b);
+}
 
 // Optional event bracket around a kernel launch (msmp_timing_*): no-ops unless the family is enabled.
 void timing_begin(int kernel, hipStream_t st);
@@ -130,3 +138,4 @@ void timing_end(int kernel, hipStream_t st);
             return (code);                     \
         }                                      \
     } while (0)
+#define RC(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)      // pass a failed entry's code on

@@ -1,19 +1,11 @@
-// The pieces of train_kernels.hip that the width-generic layer backward (wide_layer_bwd_kernel.hip) calls: the fp32-exact bf16x3 row
-// GEMM with its weight-split launch, and the batched weight-gradient launcher.  Defined in train_kernels.hip; library-internal.
+// The fp32-exact bf16x3 row GEMM and its weight-split launch (rows_gemm_kernel.hip) for the two layer backwards; library-internal.
 #pragma once
 #include "mfma_tiles.h"
 
 namespace msmp {
-
-__device__ __forceinline__ float dswish(float x) {        // d/dx x sigmoid(x)
-    const float s = sigmoidf_(x);
-    return s * (1.0f + x * (1.0f - s));
-}
-
-// ---- row GEMM: weights as pre-split bf16x3 fragments, 24-KB chunks of 32 k ----------------------------------------------------
+// weights as pre-split bf16x3 fragments, 24-KB chunks of 32 k
 constexpr int RG_CHUNK_U4 = 2 * 4 * 3 * 64;            // 16-byte fragments per 32-k chunk: [s][T][plane][lane]
 constexpr int RG_CHUNK_FLOATS = RG_CHUNK_U4 * 4;       // 24 KB
-
 struct RgPackJob {
     const float* w;      // row-major, row stride ldw
     u32x4* out;          // n_chunks * RG_CHUNK_U4 fragments
@@ -36,12 +28,4 @@ int launch_rg_pack(RgPackArgs& a, int blocks, hipStream_t st);
 // ld0; EPI 0 and 2 read / write their second tensor at row stride 128.
 int rows_gemm(int epi, const float* x, int ldx, long rows, int K, const u32x4* wfrag, const float* bias, const float* aux, float* out0,
               int ld0, float* out1, hipStream_t st);
-unsigned grid_for(long work_items);
-
-// ---- weight gradients: msmp_grad_weights_f32 on validated arguments ----------------------------------------------------------------
-constexpr int GW_MAX_JOBS = 10;
-int launch_grad_weights(int n_jobs, const float* const* a, const float* const* b, const int64_t* rows, const int* lda, const int* ldb,
-                        const int* k2, float* const* out_w, float* const* out_b, float* workspace, int64_t workspace_floats,
-                        hipStream_t stream, const float* const* b2 = nullptr, const int* ldb2 = nullptr, const int* ksplit = nullptr);
-
 }  // namespace msmp

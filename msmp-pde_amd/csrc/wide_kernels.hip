@@ -1,7 +1,7 @@
 // Width-generic pieces of the message-passing layer: the GLU classes of the reference run the SAME layers at hidden width 164
 // (experiments/models_gnn.py:1379-1523 MP_PDE_SolverLEMLinGatedGLU, models_gnn2D.py:1198-1366), which the fused 128-wide kernels
 // (four 32-channel MFMA tiles per wave, packed blobs, LDS layouts) are not built for.  Their layer is evaluated from these
-// HBM-bound kernels around msmp_linear_f32 (the fp32-exact bf16x3 row GEMM of train_kernels.hip, any K and any number of output
+// HBM-bound kernels around msmp_linear_f32 (the fp32-exact bf16x3 row GEMM of rows_gemm_kernel.hip, any K and any number of output
 // channels in 128-column groups):
 //     P, Q = msmp_linear_f32 on [h | u | pos | vars]            (message_net_1 factorised per node, :132-138)
 //     a1   = msmp_wide_gather_swish_f32(P, Q)                    Swish(P[target] + Q[source]) per edge

@@ -14,14 +14,15 @@
 //   gradients   blend / InstanceNorm backward per graph -> d upd;  d a3 = (d upd W4) Swish'(a3);  dh (+)= d a3 W3[:, h],
 //               dagg = d a3 W3[:, agg];  d a2 = dagg[tgt] / deg Swish'(a2) (over a2);  x1 = d a2 W2;
 //               S_t / S_s = x1 Swish'(a1) summed over each node's in- / out-edges in a fixed order;  dh += S_t Wp[:, h] + S_s Wq[:, h]
-//   parameters  S_t^T F, S_s^T F, d a2^T m1, d a3^T cat_n, d upd^T u1 through the weight-gradient kernel of train_kernels.hip (A in
+//   parameters  S_t^T F, S_s^T F, d a2^T m1, d a3^T cat_n, d upd^T u1 through the weight-gradient kernel of grad_weights_kernel.hip (A in
 //               128-column groups, B in column slices of at most 319), reassembled by ONE launch for all sixteen gradients.
-// Row GEMMs, the weight split and the weight-gradient launcher are those of train_kernels.hip (train_internal.h); the kernels of this file
-// are everything between them.  No atomics, no memset, fixed summation orders: two calls on the same inputs give the same bits.
+// Row GEMMs and the weight split are those of rows_gemm_kernel.hip (rows_gemm.h), the weight-gradient launcher that of
+// grad_weights_kernel.hip (grad_weights.h); the kernels of this file are everything between them.  No atomics, no memset, fixed summation orders: two calls on the same inputs give the same bits.
 #include <vector>
 
+#include "grad_weights.h"
 #include "graph_norm.h"
-#include "train_internal.h"
+#include "rows_gemm.h"
 #include "wide_frags.h"
 
 namespace msmp {

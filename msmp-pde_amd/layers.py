@@ -181,8 +181,9 @@ def mp_layer(h, u, pos_x, variables, structure, main, gate=None, eps=1e-5, dense
     """One message-passing layer (or one gated pair) on the device through msmp_mp_layer_f32.
     h [N,128], u [N,Tw], pos_x [N,1] or [N], variables [N,nv]: float32 CUDA tensors.
     dense_message: None -> module default (factorised message_net_1); True -> literal per-edge GEMM.
-    Under autograd (training) the forward is the same HIP call and the backward an explicit recompute with library GEMMs
-    and the HIP glue / weight-gradient kernels of train_kernels.hip (msmp_pde_amd.autograd)."""
+    Under autograd (training) the forward is the same HIP call and the backward one msmp_mp_layer_bwd_f32 call (layer_bwd_kernel.hip): an
+    explicit recompute on the library's own bf16x3 row GEMMs (rows_gemm_kernel.hip), its glue kernels and the weight-gradient kernels of
+    grad_weights_kernel.hip (msmp_pde_amd.autograd)."""
     gs = structure
     if gs is None or h.device.type != 'cuda':
         raise _lib.MsmpError('mp_layer needs CUDA tensors and a GraphStructure (HIP path only, no CPU fallback)')

@@ -1,4 +1,4 @@
-"""GPU tests of the training backward at the sizes where its kernels switch (train_kernels.hip).
+"""GPU tests of the training backward at the sizes where its kernels switch (layer_bwd_kernel.hip, rows_gemm_kernel.hip).
 
 `rows_gemm` runs `rows_gemm_small_kernel` (32-row workgroups, no LDS) below RG_SMALL_ROWS = 32 768 rows and `rows_gemm_kernel`
 (128-row workgroups, weights double-buffered through LDS, 16-byte epilogue stores) from there on; the elementwise and scatter

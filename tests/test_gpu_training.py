@@ -214,7 +214,7 @@ def _ragged(sizes):
 
 
 def test_backward_glue_kernels_match_float64_autograd(mp):
-    """The four glue kernels of the layer backward (train_kernels.hip) through the C-ABI, each against float64 autograd of
+    """The four glue kernels of the layer backward (layer_bwd_kernel.hip) through the C-ABI, each against float64 autograd of
     the formula it differentiates; ragged graphs (1, 2, 3, 100, 130 nodes), nodes without in-edges, tw + 1 + nv odd."""
     from msmp_pde_amd._lib import check, ptr, current_stream
     from msmp_pde_amd import autograd as A
