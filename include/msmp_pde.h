@@ -503,13 +503,15 @@ int msmp_mp_layer_bwd_f32(const float* grad_out, const float* h, const float* u,
 /* Fused AdamW step over all parameter tensors (experiments/train.py:410: optim.AdamW(model.parameters(), lr=args.lr); PyTorch
  * defaults betas (0.9, 0.999), eps 1e-8, weight_decay 1e-2): arrays of n_tensors device pointers (parameter, gradient, first and
  * second moment: fp32, contiguous) and element counts (host array); `step` = 1, 2, ... (bias correction).  One launch per 48
- * tensors.  Same update rule and order of operations as torch.optim.AdamW. */
+ * tensors.  Same update rule and order of operations as torch.optim.AdamW.  A tensor of 0 elements is legal, as it is for
+ * torch.optim.AdamW: its four pointers are not read and may be NULL.  A NULL pointer of any other tensor is MSMP_ERR_ARG. */
 int msmp_adamw_f32(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
                    float* const* exp_avg_sq, const int64_t* numel, float lr, float beta1, float beta2, float eps,
                    float weight_decay, int64_t step, msmp_stream_t stream);
 /* The same step for a captured training iteration (a hipGraph replays fixed kernel arguments): the step count lives in device
  * memory (step_dev[0], int64, advanced by this call) and so does the learning rate (lr_dev[0]; a scheduler's new value is a
- * host-to-device copy between replays).  Bias corrections are computed on the device from step_dev. */
+ * host-to-device copy between replays).  Bias corrections are computed on the device from step_dev.  Tensors of 0 elements as in
+ * msmp_adamw_f32 (pointers may be NULL); step_dev advances once per call whatever the tensors hold. */
 int msmp_adamw_capturable_f32(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
                               float* const* exp_avg_sq, const int64_t* numel, const float* lr_dev, float beta1, float beta2,
                               float eps, float weight_decay, int64_t* step_dev, msmp_stream_t stream);
@@ -535,7 +537,7 @@ int msmp_grads_finite_f32(int n_tensors, const float* const* grads, const int64_
                           int32_t* verdict_dev, void* workspace, size_t workspace_bytes, msmp_stream_t stream);
 /* msmp_adamw_capturable_f32 (experiments/train.py:410) behind that verdict: with verdict_dev[0] == 0 the same launches on the same
  * arithmetic (bit for bit, step_dev advanced by one); with any other value no parameter, moment or step_dev byte changes and
- * skipped_dev[0] (int64) advances by one. */
+ * skipped_dev[0] (int64) advances by one.  Tensors of 0 elements as in msmp_adamw_f32: their pointers may be NULL. */
 int msmp_adamw_guarded_f32(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
                            float* const* exp_avg_sq, const int64_t* numel, const float* lr_dev, float beta1, float beta2,
                            float eps, float weight_decay, int64_t* step_dev, const int32_t* verdict_dev, int64_t* skipped_dev,

@@ -182,8 +182,9 @@ static int adamw_launch(int n_tensors, float* const* params, const float* const*
         a.n = n_tensors - t0 < ADAMW_MAX_TENSORS ? n_tensors - t0 : ADAMW_MAX_TENSORS;
         int blocks = 0;
         for (int i = 0; i < a.n; ++i) {
-            MSMP_REQUIRE(params[t0 + i] && grads[t0 + i] && exp_avg[t0 + i] && exp_avg_sq[t0 + i] && numel[t0 + i] >= 0 && numel[t0 + i] < (1L << 31),
-                         MSMP_ERR_ARG, "msmp_adamw_f32: bad tensor %d", t0 + i);
+            MSMP_REQUIRE(((params[t0 + i] && grads[t0 + i] && exp_avg[t0 + i] && exp_avg_sq[t0 + i]) || numel[t0 + i] == 0) && numel[t0 + i] >= 0 &&
+                             numel[t0 + i] < (1L << 31),          // an empty tensor is never read or written: no block is its own
+                         MSMP_ERR_ARG, "msmp_adamw_f32: bad tensor %d (null pointer or element count)", t0 + i);
             a.p[i] = params[t0 + i]; a.g[i] = grads[t0 + i]; a.m[i] = exp_avg[t0 + i]; a.v[i] = exp_avg_sq[t0 + i];
             a.numel[i] = (int)numel[t0 + i];
             a.first_block[i] = blocks;
@@ -333,7 +334,8 @@ extern "C" int msmp_adamw_guarded_f32(int n_tensors, float* const* params, const
     MSMP_REQUIRE(n_tensors >= 0 && (n_tensors == 0 || (params && grads && exp_avg && exp_avg_sq && numel)), MSMP_ERR_ARG, "msmp_adamw_guarded_f32: null pointer");
     MSMP_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, MSMP_ERR_ARG, "msmp_adamw_guarded_f32: bad hyper-parameters");
     for (int i = 0; i < n_tensors; ++i)
-        MSMP_REQUIRE(params[i] && grads[i] && exp_avg[i] && exp_avg_sq[i] && numel[i] >= 0 && numel[i] < (1L << 31), MSMP_ERR_ARG,
+        MSMP_REQUIRE(((params[i] && grads[i] && exp_avg[i] && exp_avg_sq[i]) || numel[i] == 0) && numel[i] >= 0 && numel[i] < (1L << 31),
+                     MSMP_ERR_ARG,          // an empty tensor is never read or written
                      "msmp_adamw_guarded_f32: bad tensor %d (null pointer or element count)", i);
     hipLaunchKernelGGL(adamw_advance_guarded_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (long long*)step_dev, (const int*)verdict_dev,
                        (long long*)skipped_dev);

@@ -301,7 +301,8 @@ def test_explicit_backward_equals_autograd_recompute(mp):
 def test_grad_weights_kernel_shapes_and_strides(mp):
     """msmp_grad_weights_f32 through autograd.grad_weights: dW = A^T B and db = column sums for 8 pairs in one call, row
     counts that are no multiple of the 8-row step / 128-row split (1 ... 70 001), k2 from 1 to the maximum 319, row-strided
-    views for both operands; against float64.  Also: repeatable bit for bit (fixed-order reduction) and the size limit."""
+    views for both operands; against float64.  Also: repeatable bit for bit (fixed-order reduction) and the size limit.  The _cat route
+    and the tile / block / split edges, exact on integer operands: test_gpu_train_step_arith.py."""
     from msmp_pde_amd.autograd import grad_weights
     g = torch.Generator(device='cpu').manual_seed(9)
     shapes = [(1, 1), (7, 128), (129, 136), (1000, 159), (1601, 160), (9408, 284), (70001, 311), (300, 319)]
@@ -491,7 +492,8 @@ def test_output_mlp_called_the_reference_way_never_reaches_miopen(mp, name, exp)
 def test_fused_adamw_matches_torch(mp):
     """msmp_pde_amd.optim.AdamW (one HIP launch per 48 tensors) against torch.optim.AdamW over several steps of a real model
     (108 tensors of very different sizes, incl. 1-element and odd-sized ones), with a learning-rate change in between (MultiStepLR,
-    train.py:411); the packed-weight caches are invalidated by the step like with any optimizer."""
+    train.py:411); the packed-weight caches are invalidated by the step like with any optimizer.  The arithmetic of one step is pinned
+    to float64, per element and for all three forms, in test_gpu_train_step_arith.py."""
     from msmp_pde_amd import _lib
     torch.manual_seed(7)
     case = synthetic_case(mp, 'E2', bsz=2, seed=3)
@@ -547,7 +549,8 @@ def test_fused_adamw_matches_torch(mp):
 
 def test_deterministic_reduction_kernels(mp):
     """msmp_colsum_f32 / msmp_sqerr_sum_f32 (the bias gradients and the loss of a captured training step) against float64, and
-    bit-identical from run to run; the autograd wrappers route the encoder's Linear and the decoder's Conv1d bias gradients."""
+    bit-identical from run to run; the autograd wrappers route the encoder's Linear and the decoder's Conv1d bias gradients.  Exact
+    integer sums at the sizes where the kernels change path: test_gpu_train_step_arith.py."""
     from msmp_pde_amd import reductions as R
     gen = torch.Generator(device='cuda').manual_seed(3)
     for rows, cols, group in ((1, 128, 1), (1600, 128, 1), (40000, 304, 38), (77, 25, 25), (5, 4096, 1)):
