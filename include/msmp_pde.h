@@ -571,6 +571,32 @@ int msmp_batch_assemble_f32(const float* store, int64_t n_samples, int nt, int c
                             const int32_t* steps, int batch, int tw, const float* t_axis, const float* x_grid, const float* var_table,
                             int n_vars, int mode, float* x_out, float* y_out, float* pos_out, float* vars_out, msmp_stream_t stream);
 
+/* One rollout step of the reference's evaluation loops (experiments/train_helper.py:150-296 test_timestep_losses / test_unrolled_losses,
+ * :362-471 compute_L2_norms) in ONE launch: the squared error of a prediction against the labels of its window, read straight from
+ * the store of msmp_batch_assemble_f32 (no label tensor is made), the squared norm of those labels, and the time column
+ * create_next_graph (common/utils.py:454-469) writes for the next window.
+ *   store, sample_idx, steps, t_axis   as in msmp_batch_assemble_f32 (t_axis may be NULL when pos_out is NULL);
+ *   pred       [batch nx, comps tw] fp32: the model's output for the windows starting at steps[b];
+ *   err_out, nrm_out   float64, row b at + b ld (ld >= comps tw; the padding keeps its bytes);   pos_out [batch nx, 2] fp32 or NULL.
+ * For graph b with s = sample_idx[b], p = steps[b], component c < comps, k < tw, and y_i = store[s, p + k, c, i]:
+ *   d_i = pred[b nx + i, c tw + k] - y_i                         (formed in fp32, as the reference's `pred - graph.y`)
+ *   err_out[b ld + c tw + k] = sum_i (double)d_i (double)d_i
+ *   nrm_out[b ld + c tw + k] = sum_i (double)y_i (double)y_i      (the reference squares the label, train_helper.py:401)
+ *   pos_out[2 (b nx + i)]    = t_axis[p + tw]   if p + tw <= nt - tw; otherwise column 0 keeps its bytes.  Column 1 is never touched.
+ * Accumulation is float64 in a fixed order that depends on neither the grid nor `batch` (graph b's numbers are the same bits in any
+ * batch): with KP the power of two >= tw and NS = min(64, 256 / KP), a column is NS partial sums -- partial j takes the nodes i with
+ * (i mod 64) mod NS == j in ascending i -- added in ascending j.
+ * The indices live on the device, so the entry cannot refuse a bad one; the kernel never reads outside `store`: a graph whose s is
+ * outside 0 .. n_samples - 1 or whose p is outside tw .. nt - tw gets quiet NaNs in its comps tw entries of err_out and nrm_out, its
+ * pos_out rows (where written) come from clamp(p, tw, nt - tw), and every other graph is unaffected.  Refused by value before
+ * anything is launched -- MSMP_ERR_ARG: a null store, sample_idx, steps, pred, err_out or nrm_out; a null t_axis with a pos_out;
+ * batch, nx, nt or n_samples outside 1 .. 2^31 - 1; batch nx >= 2^31; comps not 1 or 2; ld < comps tw.  MSMP_ERR_UNSUPPORTED: tw
+ * outside 1..64, or nt < 2 tw.  No allocation, no synchronisation, no atomics, no memset: only pointers and sizes are baked into the
+ * launch, so a captured one replayed after steps, sample_idx or pred were overwritten evaluates the new window. */
+int msmp_eval_window_f32(const float* store, int64_t n_samples, int nt, int comps, int nx, const int32_t* sample_idx,
+                         const int32_t* steps, int batch, int tw, const float* pred, const float* t_axis, double* err_out,
+                         double* nrm_out, int64_t ld, float* pos_out, msmp_stream_t stream);
+
 /* Deterministic reductions for the PyTorch-side pieces of a training iteration (bias gradients of the encoder / decoder, the
  * loss of experiments/train_helper.py:125-141): fixed summation order, two kernel launches, no atomics, no memset -- safe inside a
  * captured (hipGraph) training step.  workspace >= msmp_reduce_workspace_bytes(cols) (cols = 1 for the scalar sum).

@@ -11,6 +11,7 @@ from .layers import Swish, GNN_Layer, GNN_LayerLin, mp_layer                  # 
 from .lem import LEM, LEMS                                                          # noqa: F401
 from . import data                                                                  # noqa: F401
 from .data import DeviceDataset, downproject, random_steps                          # noqa: F401
+from . import evaluate                                                              # noqa: F401  (the reference's test loops on a DeviceDataset)
 from . import optim                                                              # noqa: F401  (optim.AdamW: fused HIP step)
 from .solvers import (MP_PDE_Solver, MP_PDE_SolverGated, MP_PDE_SolverLEMLinGated, MP_PDE_Solver2D,   # noqa: F401
                       MP_PDE_Solver2DGated, MP_PDE_Solver2DLEMLinGated, MP_PDE_SolverLEMLin, MP_PDE_Solver2DLEMLin,

@@ -102,6 +102,8 @@ SIGNATURES = {
     'msmp_status_poison_f32': (c_int, [c_void_p, c_void_p]),
     'msmp_batch_assemble_f32': (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'msmp_eval_window_f32': (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_int64, c_void_p, c_void_p]),
     'msmp_reduce_workspace_bytes': (c_size_t, [c_int]),
     'msmp_colsum_f32': (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     'msmp_sqerr_sum_f32': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -39,6 +39,7 @@ SOURCES = {  # file -> extra flags
     'decoder_bwd_kernel.hip': [],
     'g2_gate_kernel.hip': [],
     'batch_assemble_kernel.hip': [],
+    'eval_kernel.hip': [],
     'graph_kernels.hip': ['-ffp-contract=off'],   # float64 distance compares must round like the host's
 }
 PROF = {'gw': ['-DMSMP_PROF_GW=1'], 'lem': ['-DMSMP_PROF_LEM=1'], 'tile': ['-DMSMP_PROF_TILE=1'], '1': ['-DMSMP_PROF=1'], 'edge': ['-DMSMP_PROF=1', '-DMSMP_PROF_EDGE=1'], 'proj': ['-DMSMP_PROF=1', '-DMSMP_PROF_PROJ=1']}.get(os.environ.get('MSMP_PROF', ''), [])     # phase counters in the tail kernel (scripts/prof_tail.py)
