@@ -55,24 +55,43 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def hipcc():
+    return os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+
+
+def flags(src):
+    """every flag one unit is compiled with"""
+    return COMMON + SOURCES[src]
+
+
+def compile_command(src, out, asm=False):
+    """The one definition of how a unit is compiled: to its object file, or (asm) to the assembly of the same device code."""
+    return [hipcc()] + flags(src) + (['-S', '--cuda-device-only'] if asm else ['-c']) + [os.path.join(CSRC, src), '-o', out]
+
+
+def device_asm(src, out_path):
+    """gfx950 assembly of one unit as the library contains it (tests/isa.py, the scripts/isa_*.py tools)"""
+    subprocess.run(compile_command(src, out_path, asm=True), check=True, capture_output=True)
+    return out_path
+
+
 def build(force=False, verbose=False):
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')]
     headers.append(os.path.join(ROOT, 'include', 'msmp_pde.h'))
     headers.append(os.path.abspath(__file__))          # the flags live here
     objs = []
-    for src, extra in SOURCES.items():
+    for src in SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(CSRC, src.replace('.hip', f'.lolo{LOLO}.o' if LOLO else '.precise.o' if PRECISE else ('.prof.o' if os.environ.get('MSMP_PROF') else (f'.v{VARIANT}.o' if VARIANT else '.o'))))
         if force or _stale(o, [s] + headers):
-            cmd = [hipcc] + COMMON + extra + ['-c', s, '-o', o]
+            cmd = compile_command(src, o)
             if verbose:
                 print(' '.join(cmd), flush=True)
             subprocess.check_call(cmd)
         objs.append(o)
     if force or _stale(LIB, objs):
         # -Bsymbolic: the library's own references (rocPRIM templates, ...) bind to its own definitions
-        cmd = [hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-Wl,-Bsymbolic', '-Wl,--exclude-libs,ALL', '-o', LIB] + objs
+        cmd = [hipcc(), '--offload-arch=gfx950', '-shared', '-fPIC', '-Wl,-Bsymbolic', '-Wl,--exclude-libs,ALL', '-o', LIB] + objs
         if verbose:
             print(' '.join(cmd), flush=True)
         subprocess.check_call(cmd)
@@ -80,4 +99,8 @@ def build(force=False, verbose=False):
 
 
 if __name__ == '__main__':
-    print(build(force='--force' in sys.argv, verbose=True))
+    if '--asm' in sys.argv:        # python msmp-pde_amd/build.py --asm UNIT.hip [-o FILE]
+        unit = os.path.basename(sys.argv[sys.argv.index('--asm') + 1])
+        print(device_asm(unit, sys.argv[sys.argv.index('-o') + 1] if '-o' in sys.argv else unit.replace('.hip', '.s')))
+    else:
+        print(build(force='--force' in sys.argv, verbose=True))

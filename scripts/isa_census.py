@@ -1,4 +1,4 @@
-"""Static instruction census of one kernel of an assembly listing (hipcc -S --cuda-device-only), per barrier-delimited segment:
+"""Static instruction census of one kernel of an assembly listing (python msmp-pde_amd/build.py --asm UNIT.hip -o file.s), per barrier-delimited segment:
     python scripts/isa_census.py file.s [mangled kernel name substring]"""
 import collections, sys
 lines = open(sys.argv[1]).read().splitlines()

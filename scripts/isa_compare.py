@@ -1,31 +1,14 @@
-"""Are the gfx950 kernels of two `hipcc -S --cuda-device-only` outputs the same code?
+"""Are the gfx950 kernels of two assembly files (`python msmp-pde_amd/build.py --asm UNIT.hip -o FILE`) the same code?
     python scripts/isa_compare.py before.s after.s [before_symbol=after_symbol ...]
 Kernels are paired by symbol without the argument type (a renamed kernel: give the pair, also without it).  For every pair: registers, scratch, LDS, occupancy of both, and whether the
 instruction streams are identical once symbols, labels and comments are taken out; where they are not, the instruction counts by class that
 moved."""
 import collections
-import re
+import os
 import sys
 
-
-def kernels(path):
-    text = open(path).read()
-    out = {}
-    for m in re.finditer(r'^(\w+):\s*; @\1\n(.*?)\.end_amdhsa_kernel.*?; Occupancy: (\d+)', text, re.S | re.M):
-        name, body = m.group(1).split('EvNS_')[0], m.group(2)
-        code = body.split('.section', 1)[0]
-        num = lambda key: int(re.search(r'\.amdhsa_' + key + r'\s+(\d+)', body).group(1))
-        lines = []
-        for l in code.splitlines():
-            l = re.sub(r';.*', '', l).strip()
-            if not l or l.startswith('.') and not l.endswith(':'):
-                continue
-            l = re.sub(r'\.?LBB\d+_\d+', 'L', l)
-            l = re.sub(r'_Z\w+', 'SYM', l)
-            lines.append(l)
-        out[name] = dict(lines=lines, regs=num('next_free_vgpr'), scratch=num('private_segment_fixed_size'), lds=num('group_segment_fixed_size'),
-                         occ=int(m.group(3)))
-    return out
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests'))
+from isa import parse          # noqa: E402  (the one parser of the assembly's kernel blocks)
 
 
 def klass(l):
@@ -37,7 +20,7 @@ def klass(l):
 
 
 if __name__ == '__main__':
-    a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
+    a, b = ({name.split('EvNS_')[0]: k for name, k in parse(open(path).read()).items()} for path in sys.argv[1:3])
     rename = dict(p.split('=') for p in sys.argv[3:])
     same = 0
     for name in a:
@@ -46,12 +29,13 @@ if __name__ == '__main__':
             print(f'{name}: not in {sys.argv[2]}')
             continue
         x, y = a[name], b[other]
-        res = lambda k: f"registers {k['regs']} scratch {k['scratch']} lds {k['lds']} occ {k['occ']}"
-        if x['lines'] == y['lines']:
+        res = lambda k: f'registers {k.vgpr} scratch {k.scratch} lds {k.lds} occ {k.occ}'
+        xl, yl = x.lines, y.lines
+        if xl == yl:
             same += 1
-            print(f'{other}: IDENTICAL ({len(x["lines"])} instructions; {res(y)})')
+            print(f'{other}: IDENTICAL ({len(xl)} instructions; {res(y)})')
         else:
-            cx, cy = collections.Counter(map(klass, x['lines'])), collections.Counter(map(klass, y['lines']))
+            cx, cy = collections.Counter(map(klass, xl)), collections.Counter(map(klass, yl))
             moved = ', '.join(f'{k} {cx[k]} -> {cy[k]}' for k in sorted(set(cx) | set(cy)) if cx[k] != cy[k]) or 'same counts by class, another order or other registers'
-            print(f'{other}: DIFFERENT ({len(x["lines"])} -> {len(y["lines"])} instructions; before {res(x)}; after {res(y)}): {moved}')
+            print(f'{other}: DIFFERENT ({len(xl)} -> {len(yl)} instructions; before {res(x)}; after {res(y)}): {moved}')
     print(f'{same} of {len(a)} identical')

@@ -1,6 +1,6 @@
 """Static scan of a gfx950 assembly file for prefetches that are waited for where they are issued: an `s_waitcnt vmcnt(n)` within WINDOW
 instructions behind a global / buffer load whose result it (by its count) waits for, inside a loop.
-    hipcc --offload-arch=gfx950 -O3 -S --cuda-device-only -o /tmp/k.s csrc/file.hip && python scripts/isa_early_waits.py /tmp/k.s"""
+    python msmp-pde_amd/build.py --asm UNIT.hip -o k.s && python scripts/isa_early_waits.py k.s"""
 import re, sys
 WINDOW = 12
 kern = None; body = []

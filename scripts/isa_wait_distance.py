@@ -1,6 +1,6 @@
 """For every `s_waitcnt vmcnt(n)` of one kernel in a gfx950 assembly file: which loads it completes, how many instructions behind the
 youngest of them it sits and how many barriers lie between (a prefetch waited for a few instructions behind its request is not one).
-    python scripts/isa_wait_distance.py /tmp/k.s <mangled kernel name prefix> [max distance to report, default 40]"""
+    python msmp-pde_amd/build.py --asm UNIT.hip -o k.s && python scripts/isa_wait_distance.py k.s <mangled kernel name prefix> [max distance to report, default 40]"""
 import re, sys
 src, name = sys.argv[1], sys.argv[2]
 lim = int(sys.argv[3]) if len(sys.argv) > 3 else 40

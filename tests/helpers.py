@@ -300,6 +300,23 @@ def mp():
     return msmp_pde_amd
 
 
+def built_package():
+    """msmp_pde_amd, its library built first where it is missing (hipcc cross-compiles gfx950 without a GPU)"""
+    import sys
+    import msmp_pde_amd
+    if not os.path.exists(msmp_pde_amd.LIB_PATH):
+        sys.path.insert(0, os.path.dirname(os.path.dirname(GOLDEN)))
+        import __graft_entry__
+        __graft_entry__.build()
+    return msmp_pde_amd
+
+
+@pytest.fixture(scope='module')
+def L():
+    """the library's ctypes handle, for the C-ABI tests that launch nothing (test_cabi_*.py)"""
+    return built_package().lib()
+
+
 WIDE_SWITCHES = (b'wide_msg', b'wide_tail', b'wide_proj', b'lem_wide', b'split')
 _SHIPPED_SWITCHES = {}
 

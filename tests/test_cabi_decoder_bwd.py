@@ -4,11 +4,10 @@ return value with msmp_last_error naming the entry, every window / width the ref
 (the size query returns 0 for it), a workspace one byte short is refused, and the switch stores the value it is given."""
 import os
 import re
-import sys
 
 import pytest
 
-from helpers import abi_versions_agree
+from helpers import L, abi_versions_agree        # noqa: F401  (L: a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TRAIN_FWD = ('msmp_decoder_train_fwd_f32', 'msmp_decoder2d_train_fwd_f32', 'msmp_decoder_gated_train_fwd_f32', 'msmp_decoder2d_gated_train_fwd_f32')
@@ -29,16 +28,6 @@ KIND = {'msmp_decoder_bwd_f32': (1, 0), 'msmp_decoder2d_bwd_f32': (2, 0), 'msmp_
 
 def pointers(name):
     return [k for k in ORDER[name] if k not in SCALARS]
-
-
-@pytest.fixture(scope='module')
-def L():
-    import msmp_pde_amd
-    if not os.path.exists(msmp_pde_amd.LIB_PATH):       # hipcc cross-compiles gfx950 without a GPU
-        sys.path.insert(0, ROOT)
-        import __graft_entry__
-        __graft_entry__.build()
-    return msmp_pde_amd.lib()
 
 
 def call(L, name, **kw):

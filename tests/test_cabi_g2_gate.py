@@ -8,22 +8,12 @@ import sys
 
 import pytest
 
-from helpers import abi_versions_agree
+from helpers import L, abi_versions_agree        # noqa: F401  (L: a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FWD, BWD, WS = 'msmp_g2_gate_blend_f32', 'msmp_g2_gate_blend_bwd_f32', 'msmp_g2_gate_blend_bwd_workspace_bytes'
 FWD_POINTERS = ('h', 'gate', 'main', 'out_rowptr', 'out_nbr', 'out')           # tau_out may be NULL: tau is then not saved
 BWD_POINTERS = ('grad_out', 'h', 'gate', 'main', 'tau', 'out_rowptr', 'out_nbr', 'in_rowptr', 'in_col', 'dh', 'da', 'db', 'workspace')
-
-
-@pytest.fixture(scope='module')
-def L():
-    import msmp_pde_amd
-    if not os.path.exists(msmp_pde_amd.LIB_PATH):       # hipcc cross-compiles gfx950 without a GPU
-        sys.path.insert(0, ROOT)
-        import __graft_entry__
-        __graft_entry__.build()
-    return msmp_pde_amd.lib()
 
 
 def call(L, name, **kw):

@@ -3,25 +3,14 @@
 (width, time_window) other than (164, 25) is refused by value as unsupported, and the switch stores the value it is given."""
 import os
 import re
-import sys
 
 import pytest
 
-from helpers import abi_versions_agree
+from helpers import L, abi_versions_agree        # noqa: F401  (L: a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ('msmp_decoder_gated_f32', 'msmp_decoder2d_gated_f32')
 POINTERS = ('h', 'u', 'gate_w1', 'gate_b1', 'gate_w2', 'gate_b2', 'diff_w1', 'diff_b1', 'diff_w2', 'diff_b2', 'out')
-
-
-@pytest.fixture(scope='module')
-def L():
-    import msmp_pde_amd
-    if not os.path.exists(msmp_pde_amd.LIB_PATH):       # hipcc cross-compiles gfx950 without a GPU
-        sys.path.insert(0, ROOT)
-        import __graft_entry__
-        __graft_entry__.build()
-    return msmp_pde_amd.lib()
 
 
 def call(L, name, **kw):

@@ -2,23 +2,11 @@
 msmp_knn_graph_f64): a value outside what the kernels are built for is refused by return code before anything is launched, with a message
 in msmp_last_error.  The pointers are fake addresses: a call that got as far as a launch would need a device, and the file runs without
 one."""
-import os
-import sys
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from helpers import L        # noqa: F401  (a fixture)
+
 OK, ERR_ARG, ERR_UNSUPPORTED = 0, -1, -2          # include/msmp_pde.h
-
-
-@pytest.fixture(scope='module')
-def L():
-    import msmp_pde_amd
-    if not os.path.exists(msmp_pde_amd.LIB_PATH):       # hipcc cross-compiles gfx950 without a GPU
-        sys.path.insert(0, ROOT)
-        import __graft_entry__
-        __graft_entry__.build()
-    return msmp_pde_amd.lib()
 
 
 def call(L, entry, **kw):

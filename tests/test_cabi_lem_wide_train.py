@@ -4,11 +4,10 @@ outside the range, pack and launch entries refuse null pointers by return value,
 and stores the value it is given, and the retired 128-wide entries and their section of the inference blob are gone."""
 import os
 import re
-import sys
 
 import pytest
 
-from helpers import abi_versions_agree
+from helpers import L, abi_versions_agree        # noqa: F401  (L: a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ('msmp_packed_lem_wide_train_floats', 'msmp_pack_lem_wide_train_f32', 'msmp_packed_lem_wide_bwd_floats', 'msmp_pack_lem_wide_bwd_f32',
@@ -18,16 +17,6 @@ RETIRED = ('msmp_lem_saved_floats', 'msmp_lem_train_fwd_f32', 'msmp_packed_lem_b
 
 def _header():
     return open(os.path.join(ROOT, 'include', 'msmp_pde.h')).read()
-
-
-@pytest.fixture(scope='module')
-def L():
-    import msmp_pde_amd
-    if not os.path.exists(msmp_pde_amd.LIB_PATH):       # hipcc cross-compiles gfx950 without a GPU
-        sys.path.insert(0, ROOT)
-        import __graft_entry__
-        __graft_entry__.build()
-    return msmp_pde_amd.lib()
 
 
 def test_header_declares_and_library_exports_the_entries(L):

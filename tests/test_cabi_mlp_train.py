@@ -4,11 +4,10 @@ size entries follow the documented formulas and refuse shapes outside the range,
 pointers by return value before anything is launched, and the switch "mlp_train" is documented, listed and stores the value it is given."""
 import os
 import re
-import sys
 
 import pytest
 
-from helpers import abi_versions_agree
+from helpers import L, abi_versions_agree        # noqa: F401  (L: a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ('msmp_packed_mlp_train_floats', 'msmp_pack_mlp_train_f32', 'msmp_mlp_train_saved_floats', 'msmp_mlp_train_fwd_f32',
@@ -18,16 +17,6 @@ FORMS = ((2, 1), (1, 1), (1, 2))        # (layers, heads)
 
 def _header():
     return open(os.path.join(ROOT, 'include', 'msmp_pde.h')).read()
-
-
-@pytest.fixture(scope='module')
-def L():
-    import msmp_pde_amd
-    if not os.path.exists(msmp_pde_amd.LIB_PATH):       # hipcc cross-compiles gfx950 without a GPU
-        sys.path.insert(0, ROOT)
-        import __graft_entry__
-        __graft_entry__.build()
-    return msmp_pde_amd.lib()
 
 
 def pack(L, layers, heads, k, w):

@@ -5,26 +5,15 @@ pointers, bad counts and a short workspace are refused by return value with msmp
 import ctypes
 import os
 import re
-import sys
 
 import pytest
 
-from helpers import abi_versions_agree
+from helpers import L, abi_versions_agree        # noqa: F401  (L: a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FINITE, GUARDED, POISON, QUERY = 'msmp_grads_finite_f32', 'msmp_adamw_guarded_f32', 'msmp_status_poison_f32', 'msmp_grads_finite_workspace_bytes'
 N = 3
 NUMEL = (1, 5000, 12345)          # 1 + 2 + 4 chunks of 4096 elements
-
-
-@pytest.fixture(scope='module')
-def L():
-    import msmp_pde_amd
-    if not os.path.exists(msmp_pde_amd.LIB_PATH):       # hipcc cross-compiles gfx950 without a GPU
-        sys.path.insert(0, ROOT)
-        import __graft_entry__
-        __graft_entry__.build()
-    return msmp_pde_amd.lib()
 
 
 def table(values):

@@ -3,24 +3,13 @@ exports them, the blob size follows the padded width, the in-degree cap covers t
 arguments are refused by return value with msmp_last_error set."""
 import os
 import re
-import sys
 
 import pytest
 
-from helpers import abi_versions_agree
+from helpers import L, abi_versions_agree        # noqa: F401  (L: a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ('msmp_packed_wide_msg_floats', 'msmp_pack_wide_msg_f32', 'msmp_wide_message_max_in_degree', 'msmp_wide_message_f32')
-
-
-@pytest.fixture(scope='module')
-def L():
-    import msmp_pde_amd
-    if not os.path.exists(msmp_pde_amd.LIB_PATH):       # hipcc cross-compiles gfx950 without a GPU
-        sys.path.insert(0, ROOT)
-        import __graft_entry__
-        __graft_entry__.build()
-    return msmp_pde_amd.lib()
 
 
 def test_header_declares_and_library_exports_the_entry(L):

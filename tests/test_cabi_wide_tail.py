@@ -1,21 +1,9 @@
 """CPU test (no kernel launched): the C-ABI size queries of the layer forward / backward accept message_net_1 tails of up to four
 32-column chunks (tw + 1 + nv <= 128: the 2-D classes at time_window 50) and refuse wider ones."""
-import os
-import sys
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from helpers import L        # noqa: F401  (a fixture)
 
-
-@pytest.fixture(scope='module')
-def L():
-    import msmp_pde_amd
-    if not os.path.exists(msmp_pde_amd.LIB_PATH):       # hipcc cross-compiles gfx950 without a GPU
-        sys.path.insert(0, ROOT)
-        import __graft_entry__
-        __graft_entry__.build()
-    return msmp_pde_amd.lib()
 
 
 @pytest.mark.parametrize('tw,nv,stride', [(25, 2, 32), (50, 3, 64), (70, 3, 96), (100, 3, 128), (100, 8, 128), (127, 1, 160)])

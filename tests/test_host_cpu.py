@@ -8,19 +8,14 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import load, sd_of, graph_of, EXPERIMENTS, synthetic_case, DEEP_CASES, RECURRENT_CASES, recurrent_id, load_recurrent, deep_shapes
+from helpers import load, sd_of, graph_of, EXPERIMENTS, synthetic_case, DEEP_CASES, RECURRENT_CASES, recurrent_id, load_recurrent, deep_shapes, built_package
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope='module')
 def mp():
-    import msmp_pde_amd
-    if not os.path.exists(msmp_pde_amd.LIB_PATH):       # hipcc cross-compiles gfx950 without a GPU
-        sys.path.insert(0, ROOT)
-        import __graft_entry__
-        __graft_entry__.build()
-    return msmp_pde_amd
+    return built_package()
 
 
 def test_cabi_exports_every_declared_symbol(mp):

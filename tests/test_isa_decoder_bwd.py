@@ -1,17 +1,11 @@
 """Static check of the gfx950 code of the decoder backward kernels (no GPU: hipcc cross-compiles here, as in test_isa_gated_decoder.py).
 Hard limits of every instantiated decoder_bwd_kernel: no scratch memory, and an LDS footprint that lets at least two workgroups share a
 compute unit.  The vector-register count is printed (it goes into the profile note), not held to a number."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'msmp-pde_amd', 'csrc')
-HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
-pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason='hipcc not found')
+import isa
+
+pytestmark = isa.needs_compiler()
 LDS_PER_CU = 163840
 # DecBwd<C, R, NETS, TW, K1, S1, K2, MODE>: 1-D tw 20 / 25 / 50 with the Euler update (MODE 1) and without (0), 2-D tw 25 / 50, gated 1-D / 2-D
 GEOMETRIES = [(1, 128, 1, 20, 15, 4, 10, 1), (1, 128, 1, 25, 16, 3, 14, 1), (1, 128, 1, 50, 12, 2, 10, 1),
@@ -20,26 +14,13 @@ GEOMETRIES = [(1, 128, 1, 20, 15, 4, 10, 1), (1, 128, 1, 25, 16, 3, 14, 1), (1, 
               (1, 82, 2, 25, 6, 2, 15, 2), (2, 82, 2, 25, 6, 2, 15, 2)]
 
 
-@pytest.fixture(scope='module')
-def isa(tmp_path_factory):
-    d = tmp_path_factory.mktemp('isa_decoder_bwd')
-    s = d / 'decoder_bwd_kernel.s'
-    subprocess.run([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '-I', os.path.join(ROOT, 'include'), '-I', CSRC, '-S', '--cuda-device-only',
-                    '-o', str(s), os.path.join(CSRC, 'decoder_bwd_kernel.hip')], check=True, capture_output=True, cwd=str(d))
-    return open(s).read()
+def kernels():
+    """{mangled name: kernel} of every decoder_bwd_kernel instantiation in the assembly"""
+    return {k.name: k for k in isa.find('decoder_bwd_kernel.hip', r'_ZN4msmp\d+decoder_bwd_kernel')}
 
 
-def kernels(isa):
-    """{mangled name: resources} of every decoder_bwd_kernel instantiation in the assembly"""
-    found = {}
-    for k in re.finditer(r'^(_ZN4msmp\d+decoder_bwd_kernel\w*):.*?\.end_amdhsa_kernel', isa, re.S | re.M):
-        num = lambda key: int(re.search(r'\.amdhsa_' + key + r'\s+(\d+)', k.group(0)).group(1))
-        found[k.group(1)] = {'vgpr': num('next_free_vgpr'), 'scratch': num('private_segment_fixed_size'), 'lds': num('group_segment_fixed_size')}
-    return found
-
-
-def test_every_geometry_is_instantiated(isa):
-    names = kernels(isa)
+def test_every_geometry_is_instantiated():
+    names = kernels()
     assert len(names) == len(GEOMETRIES), sorted(names)
     for g in GEOMETRIES:
         args = 'DecBwdI' + ''.join('Li%dE' % v for v in g)
@@ -47,10 +28,10 @@ def test_every_geometry_is_instantiated(isa):
 
 
 @pytest.mark.parametrize('geometry', GEOMETRIES)
-def test_no_scratch_and_two_workgroups_per_compute_unit(isa, geometry):
+def test_no_scratch_and_two_workgroups_per_compute_unit(geometry):
     args = 'DecBwdI' + ''.join('Li%dE' % v for v in geometry)
-    (name, r), = [(n, r) for n, r in kernels(isa).items() if args in n]
-    print(f'decoder_bwd_kernel<DecBwd<{", ".join(map(str, geometry))}>>: {r["vgpr"]} vector registers, {r["lds"]} bytes of LDS '
-          f'({LDS_PER_CU // r["lds"]} workgroups per CU by LDS), scratch {r["scratch"]}')
-    assert r['scratch'] == 0, (name, r)
-    assert r['lds'] > 0 and LDS_PER_CU // r['lds'] >= 2, (name, r)
+    r, = [r for n, r in kernels().items() if args in n]
+    print(f'decoder_bwd_kernel<DecBwd<{", ".join(map(str, geometry))}>>: {r.vgpr} vector registers, {r.lds} bytes of LDS '
+          f'({LDS_PER_CU // r.lds} workgroups per CU by LDS), scratch {r.scratch}')
+    assert r.scratch == 0, r
+    assert r.lds > 0 and LDS_PER_CU // r.lds >= 2, r

@@ -9,42 +9,24 @@ nodes took 1.74 ms against 1.63 ms of the retired 128-wide kernel (163 registers
 bound -- two workgroups per CU there take the time of the retired kernel's three (1.90 - 1.93 ms against 1.94 - 1.95 ms).
 At KT = 5 .. 7 (KT = 6: width 164, the GLU classes) both kernels stay at <= 168: three waves per SIMD (512 / 3, allocated in eights), which at
 KT = 6 is two six-wave workgroups per CU; above it only one fits."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'msmp-pde_amd', 'csrc')
-HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
-pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason='hipcc not found')
+import isa
+
+pytestmark = isa.needs_compiler()
 KERNELS = {'fwd': '_ZN4msmp25lem_wide_train_fwd_kernelILi%dEE', 'bptt': '_ZN4msmp20lem_wide_bptt_kernelILi%dEE'}
 KT4_REGISTERS = {'fwd': 168, 'bptt': 180}
 THREE_WAVES_PER_SIMD = 168
 
 
-@pytest.fixture(scope='module')
-def isa(tmp_path_factory):
-    d = tmp_path_factory.mktemp('isa_lem_wide_train')
-    s = d / 'lem_wide_train_kernel.s'
-    subprocess.run([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '-I', os.path.join(ROOT, 'include'), '-I', CSRC, '-S', '--cuda-device-only',
-                    '-o', str(s), os.path.join(CSRC, 'lem_wide_train_kernel.hip')], check=True, capture_output=True, cwd=str(d))
-    return open(s).read()
-
-
 @pytest.mark.parametrize('kt', range(1, 9))
 @pytest.mark.parametrize('which', sorted(KERNELS))
-def test_registers_scratch_and_lds(isa, which, kt):
-    k = re.search(r'^' + KERNELS[which] % kt + r'\w*:.*?\.end_amdhsa_kernel', isa, re.S | re.M)
-    assert k, (which, kt)
-    body = k.group(0)
-    num = lambda key: int(re.search(r'\.amdhsa_' + key + r'\s+(\d+)', body).group(1))
+def test_registers_scratch_and_lds(which, kt):
+    k = isa.kernel('lem_wide_train_kernel.hip', KERNELS[which] % kt)
     budget = KT4_REGISTERS[which] if kt == 4 else THREE_WAVES_PER_SIMD if kt in (5, 6, 7) else min(512, 512 // ((kt + 3) // 4))
-    print(which, kt, 'registers', num('next_free_vgpr'), 'lds', num('group_segment_fixed_size'))
-    assert num('private_segment_fixed_size') == 0, (which, kt, num('private_segment_fixed_size'))
-    assert num('next_free_vgpr') <= budget, (which, kt, num('next_free_vgpr'), budget)
-    assert num('group_segment_fixed_size') == 6144 * kt, (which, kt, num('group_segment_fixed_size'))
-    assert len(re.findall(r'v_mfma_f32_32x32x16_bf16', body)) >= 4 * kt * 12, (which, kt)       # 4 GEMMs x KT k-tiles x 2 k-steps x 6 products
-    assert not re.search(r'v_mfma_\w+_f16', body), (which, kt)
+    print(which, kt, 'registers', k.vgpr, 'lds', k.lds)
+    assert k.scratch == 0, k
+    assert k.vgpr <= budget, (k, budget)
+    assert k.lds == 6144 * kt, k
+    assert k.count(r'v_mfma_f32_32x32x16_bf16') >= 4 * kt * 12, k       # 4 GEMMs x KT k-tiles x 2 k-steps x 6 products
+    assert not k.count(r'v_mfma_\w+_f16'), k

@@ -7,17 +7,11 @@ fp16 MFMA: the fp32-exact path has no input range).
 At KT = 4 (width 128) and KT = 6 (width 164, the GLU classes) the register counts are pinned to what the kernels compile to, as upper bounds
 (profiles/r21a_mlp_train.md): at most 128 registers everywhere, i.e. four waves per SIMD and LDS (24 / 36 KB per workgroup), not registers,
 decides how many workgroups a CU holds."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'msmp-pde_amd', 'csrc')
-HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
-pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason='hipcc not found')
+import isa
+
+pytestmark = isa.needs_compiler()
 KERNELS = {'fwd': '_ZN4msmp20mlp_train_fwd_kernelILi%dELi%dEE', 'bwd': '_ZN4msmp20mlp_train_bwd_kernelILi%dELi%dEE'}
 PINNED = {('fwd', 4, 2): 84, ('fwd', 4, 1): 84, ('bwd', 4, 2): 112, ('bwd', 4, 1): 116,
           ('fwd', 6, 2): 80, ('fwd', 6, 1): 80, ('bwd', 6, 2): 96, ('bwd', 6, 1): 87}
@@ -26,27 +20,15 @@ PINNED = {('fwd', 4, 2): 84, ('fwd', 4, 1): 84, ('bwd', 4, 2): 112, ('bwd', 4, 1
 MIN_MFMA = {('fwd', 2): lambda kt: 12 + 12 * kt, ('fwd', 1): lambda kt: 12, ('bwd', 2): lambda kt: 12 * kt + 12, ('bwd', 1): lambda kt: 12}
 
 
-@pytest.fixture(scope='module')
-def isa(tmp_path_factory):
-    d = tmp_path_factory.mktemp('isa_mlp_train')
-    s = d / 'mlp_train_kernel.s'
-    subprocess.run([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '-I', os.path.join(ROOT, 'include'), '-I', CSRC, '-S', '--cuda-device-only',
-                    '-o', str(s), os.path.join(CSRC, 'mlp_train_kernel.hip')], check=True, capture_output=True, cwd=str(d))
-    return open(s).read()
-
-
 @pytest.mark.parametrize('kt', range(1, 9))
 @pytest.mark.parametrize('layers', (2, 1))
 @pytest.mark.parametrize('which', sorted(KERNELS))
-def test_registers_scratch_and_lds(isa, which, layers, kt):
-    k = re.search(r'^' + KERNELS[which] % (kt, layers) + r'\w*:.*?\.end_amdhsa_kernel', isa, re.S | re.M)
-    assert k, (which, layers, kt)
-    body = k.group(0)
-    num = lambda key: int(re.search(r'\.amdhsa_' + key + r'\s+(\d+)', body).group(1))
+def test_registers_scratch_and_lds(which, layers, kt):
+    k = isa.kernel('mlp_train_kernel.hip', KERNELS[which] % (kt, layers))
     budget = PINNED.get((which, kt, layers), min(512, 512 // ((kt + 3) // 4)))
-    print(which, 'layers', layers, 'KT', kt, 'registers', num('next_free_vgpr'), 'lds', num('group_segment_fixed_size'))
-    assert num('private_segment_fixed_size') == 0, (which, layers, kt, num('private_segment_fixed_size'))
-    assert num('next_free_vgpr') <= budget, (which, layers, kt, num('next_free_vgpr'), budget)
-    assert num('group_segment_fixed_size') == 6144 * kt, (which, layers, kt, num('group_segment_fixed_size'))
-    assert len(re.findall(r'v_mfma_f32_32x32x16_bf16', body)) >= MIN_MFMA[which, layers](kt), (which, layers, kt)
-    assert not re.search(r'v_mfma_\w+_f16', body), (which, layers, kt)
+    print(which, 'layers', layers, 'KT', kt, 'registers', k.vgpr, 'lds', k.lds)
+    assert k.scratch == 0, k
+    assert k.vgpr <= budget, (k, budget)
+    assert k.lds == 6144 * kt, k
+    assert k.count(r'v_mfma_f32_32x32x16_bf16') >= MIN_MFMA[which, layers](kt), k
+    assert not k.count(r'v_mfma_\w+_f16'), k
