@@ -105,7 +105,9 @@ int msmp_last_status(int* flags_out, int reset);
  *   "wide_tail" 1: the host's no-grad layer at widths other than 128 evaluates the node half of a layer (both heads of a gated
  *             pair) as one msmp_wide_node_tail_f32 launch on graphs of up to 128 nodes; 0 (default): per head a concatenation and two
  *             msmp_linear_f32, then msmp_wide_norm_blend_f32 (the entry itself does not read the key).  The host takes the fused launch only while "wide_msg",
- *             "split" and "lem_wide" are 1 as well, so each of those keeps selecting the path it selected before this kernel.
+ *             "split" and "lem_wide" are 1 as well, so each of those keeps selecting the path it selected before this kernel.  The
+ *             fused launch runs update_net_2 CENTRED per graph (on Swish(z_n) - Swish(z of the graph's first node), without its bias b4:
+ *             InstanceNorm removes the constant), so b4 does not enter its result.
  *   "wide_proj" 1: the host's no-grad layer at widths other than 128 evaluates the P / Q projections of message_net_1 (both heads of
  *             a gated pair) as one msmp_wide_node_proj_f32 launch; 0 (default): a concatenation [h | u | pos | vars] and two msmp_linear_f32 per head
  *             (the entry itself does not read the key).  The host takes the fused launch only while "wide_msg", "split" and "lem_wide" are 1
@@ -834,6 +836,11 @@ int msmp_wide_message_f32(const float* p, const float* q, const int32_t* rowptr,
  *   y_k = w4_k z_k + b4_k                             update_net_2 (GNN_LayerLin: no activation, no residual)
  *   n_k = InstanceNorm of y_k per graph and channel, biased variance, eps (:129)
  *   out = n_main   without a gate head;   out = (1 - tau) h + tau Swish(n_main),  tau = sigmoid(n_gate)   with one (:1486-1489).
+ * update_net_2 is evaluated CENTRED: n_k does not change when a per-graph, per-channel constant is taken from y_k, so the kernel forms
+ * w4_k 2^6 (z_n - z_ref), z_ref the row of the graph's first node, from zero accumulators.  The fp32 accumulator then rounds relative to the
+ * variation of y over the graph, which the norm divides by, not to |y|, and the lo half of the operand's fp16 split stays out of the
+ * fp16 denormals (|z_n - z_ref| must stay below 1024; beyond that the statistics are not finite and raise MSMP_STATUS_NONFINITE).  b4 keeps its place in the blob and is NOT read: the result does
+ * not depend on it (bitwise, as long as it does not move the power of two chosen for (w4, b4)).
  * One workgroup per graph and fixed-order sums: a graph's rows do not depend on the batch around it or on its position, and two runs
  * give the same bits.  fp16-split MFMA arithmetic of the default path with node rows scaled by 2^8: an h or agg element with |x| > 255
  * or not finite raises MSMP_STATUS_NODE_SATURATED, statistics that are not finite raise MSMP_STATUS_NONFINITE.

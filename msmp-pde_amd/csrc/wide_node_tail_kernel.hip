@@ -20,7 +20,17 @@
 //     registers through a three-slot ring (as in lem_wide_kernel.hip) and serves the two column blocks of the pair.  Sharing a pass over the
 //     weights among all four blocks would halve the L2 traffic but needs 64 more accumulator registers for z beside the 128 of y
 //     and K-chunked staging of every operand; with two blocks the stream is 2 KB per wave and k-step against six MFMAs.
-// Arithmetic of wide_frags.h, with the node rows scaled by 2^8 and split (split8_node) and the accumulators initialised with the scaled bias.
+//   * update_net_2 is CENTRED per graph and head (as in the 128-wide tail): InstanceNorm removes any per-graph, per-channel
+//     constant of y, so GEMM 2 runs on Swish(z_n) - Swish(z_ref), z_ref the graph's first node, from zero accumulators and without b4
+//     (the blob keeps b4's place; the kernel never reads it).  The fp32 accumulator of the three-MFMA split rounds relative to what it
+//     holds: now the variation of y over the graph, which is what the norm divides by, instead of |y|.  Wave T publishes only its own 32
+//     channels of z, so Swish(z_ref) is wave-local: one 32-float LDS row per head and wave behind the fragments, written by the two
+//     lanes that hold node 0 in pair 0 and read back (as a broadcast) by the same wave in both pairs; no barrier of its own.
+//     The difference is multiplied by 2^6 before its hi / lo split (WNT_Z_SCALE; the Swish operands of the 128-wide path carry the same
+//     factor, |difference| < 1024): untrained, Swish(z) is of order 0.02, and the lo half of an unscaled value below 2^-3 is an fp16
+//     denormal with an absolute step of 2^-24 -- an operand error that no centring removes and that set the error of this kernel
+//     (scripts/diag_wide_tail.py: 7.9e-7 rms per layer pair without the factor, 1.5e-7 with it; numpy float32 2.4e-7).
+// Arithmetic of wide_frags.h, with the node rows scaled by 2^8 and split (split8_node) and GEMM 1's accumulators initialised with the scaled bias.
 // Rows / columns W .. Wp - 1 of the packed weights and biases are exact zeros.  One workgroup per graph and fixed-order sums: the result
 // of a graph does not depend on the batch around it, on its position, or on the run.
 #include "wide_frags.h"
@@ -29,8 +39,13 @@ namespace msmp {
 
 constexpr int WNT_MAX_NODES = 128;            // four 32-node column blocks
 constexpr int WNT_NB = 2;                     // column blocks that share one pass over the weights
+constexpr float WNT_Z_SCALE = 64.0f;          // update_net_2's operand Swish(z_n) - Swish(z_ref) is split as this multiple; y carries it too
 
-// packed blob (floats): scales [8]: 2^s3, 2^s4, 0, 0, 2^-(s3 + 8), 2^-s4, 0, 0 | b3 2^(s3 + 8) [Wp] | b4 2^s4 [Wp] |
+// LDS of a workgroup of kt waves: the fragments [k-step 4 kt + 1][plane 2][block NB][lane 64] half8, then Swish(z_ref) [head 2][Wp] floats
+__host__ __device__ constexpr int wnt_frag_bytes(int kt) { return (4 * kt + 1) * 2 * WNT_NB * 1024; }
+__host__ __device__ constexpr int wnt_lds_bytes(int kt) { return wnt_frag_bytes(kt) + 2 * 32 * kt * 4; }
+
+// packed blob (floats): scales [8]: 2^s3, 2^s4, 0, 0, 2^-(s3 + 8), 2^-s4, 0, 0 | b3 2^(s3 + 8) [Wp] | b4 2^s4 [Wp] (unread: centring) |
 //   w3: [T KT][k-step 4 KT + 1][plane 2: hi, lo][lane 64][8 halfs], natural k order: k-steps 0 .. 2 KT - 1 the h columns,
 //       2 KT .. 4 KT - 1 the agg columns, the last one the variables (k 0 .. nv - 1, zeros above) |
 //   w4: [T KT][k-step 2 KT][plane 2][lane 64][8 halfs], acc order (split_k_acc: its B operand is published from accumulators)
@@ -92,7 +107,7 @@ __global__ void pack_wide_tail_kernel(WideTailPackArgs a) {
 struct WideTailHead {
     const float* agg;           // [N, ld]; null: no such head
     const float* scales;
-    const float *b3, *b4;       // [Wp], scaled
+    const float* b3;            // [Wp], scaled
     const half8 *w3, *w4;
 };
 
@@ -196,7 +211,7 @@ __device__ __forceinline__ float wnt_half_wave_sum(float v) {
     return v;
 }
 
-// y (accumulators of all four column blocks, still times 2^s4) -> InstanceNorm over the graph's cnt nodes, in place: two passes, biased
+// y (accumulators of all four column blocks, still times 1 / inv_scale = 2^s4 WNT_Z_SCALE) -> InstanceNorm over the graph's cnt nodes, in place: two passes, biased
 // variance, the formula of wide_norm_blend_kernel.  Register r of lane (c, hh) is channel 32 T + acc_row(r, hh) of node 32 block + c.
 __device__ __forceinline__ void wnt_instance_norm(f32x16 (&y)[4], float inv_scale, int cnt, int c, float eps, bool& bad) {
     const float inv_cnt = 1.0f / (float)cnt;
@@ -223,8 +238,9 @@ __device__ __forceinline__ void wnt_instance_norm(f32x16 (&y)[4], float inv_scal
     }
 }
 
-// one head on one pair of column blocks: stage agg + vars, GEMM 1, Swish -> z fragments, GEMM 2 into y[0 .. 1] (the pair's blocks)
-template <int KT>
+// one head (HEAD 0: gate, 1: main) on one pair of column blocks: stage agg + vars, GEMM 1, Swish(z) - Swish(z_ref) -> z fragments, GEMM 2
+// into y[0 .. 1] (the pair's blocks).  Node 0 of the graph is column c = 0 of block 0 of pair 0: lanes 0 and 32 hold its 16 + 16 channels.
+template <int KT, int HEAD>
 __device__ __forceinline__ void wnt_head_pair(const WideTailArgs& a, const WideTailHead& hd, int n0, int cnt, int pbase, int T, int c, int hh,
                                               int tid, unsigned lo, char* lds, f32x16& y0, f32x16& y1, unsigned& worst) {
     constexpr int KS = 2 * KT, HB = KS * 2 * WNT_NB * 1024;       // the h area; the agg + vars area (and z over it) follows
@@ -244,6 +260,8 @@ __device__ __forceinline__ void wnt_head_pair(const WideTailArgs& a, const WideT
     wnt_ring_start(ring, w4, lo, KS);
     __syncthreads();                // every wave has read the agg area: z may be written over it
     const float inv3 = uniform_ro(hd.scales, 4);
+    // this wave's row of Swish(z_ref), in accumulator order: [hh][register]
+    float* const zref = reinterpret_cast<float*>(lds + wnt_frag_bytes(KT)) + (HEAD * KT + T) * 32 + 16 * hh;
 #pragma unroll
     for (int blk = 0; blk < WNT_NB; ++blk) {
 #pragma unroll
@@ -251,12 +269,25 @@ __device__ __forceinline__ void wnt_head_pair(const WideTailArgs& a, const WideT
             float v[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = swishf(z[blk][8 * s + j] * inv3);
+            if (pbase == 0 && blk == 0) {       // the graph's first node is here: its values stay for this pair and the next
+                if (c == 0) {
+                    *reinterpret_cast<f32x4*>(zref + 8 * s) = f32x4{v[0], v[1], v[2], v[3]};
+                    *reinterpret_cast<f32x4*>(zref + 8 * s + 4) = f32x4{v[4], v[5], v[6], v[7]};
+                }
+                __builtin_amdgcn_wave_barrier();        // written and read by this wave only
+            }
+            const f32x4 r0 = *reinterpret_cast<const f32x4*>(zref + 8 * s), r1 = *reinterpret_cast<const f32x4*>(zref + 8 * s + 4);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = (v[j] - (j < 4 ? r0[j] : r1[j - 4])) * WNT_Z_SCALE;
             publish_split<WNT_NB>(v, lds + HB + lane * 16, 2 * T + s, blk);
         }
         __builtin_amdgcn_sched_barrier(0);      // (one column block's activations at a time)
     }
     f32x16 y[WNT_NB];
-    acc_bias_init(hd.b4 + 32 * T + 4 * hh, y);
+#pragma unroll
+    for (int blk = 0; blk < WNT_NB; ++blk)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) y[blk][r] = 0.f;       // no b4: InstanceNorm removes it
     __syncthreads();                // z is complete
     wnt_gemm<KS>(ring, w4, lo, lds + HB + lane * 16, y);
     __syncthreads();                // every wave has read z: the next agg rows may be staged over it
@@ -267,8 +298,9 @@ __device__ __forceinline__ void wnt_head_pair(const WideTailArgs& a, const WideT
 template <int KT>
 __global__ __launch_bounds__(64 * KT, 2) void wide_node_tail_kernel(WideTailArgs a) {
     constexpr int KS = 2 * KT;
-    // one LDS object: h fragments of the pair [k-step 2 KT][plane][block][lane] | agg fragments + the variables' k-step, later z
-    __shared__ __attribute__((aligned(16))) char lds[(2 * KS + 1) * 2 * WNT_NB * 1024];
+    // one LDS object: h fragments of the pair [k-step 2 KT][plane][block][lane] | agg fragments + the variables' k-step, later z |
+    // Swish(z_ref) [head][Wp]
+    __shared__ __attribute__((aligned(16))) char lds[wnt_lds_bytes(KT)];
     const int tid = threadIdx.x;
     const int T = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int W = a.width, ld = a.ld;
@@ -296,19 +328,19 @@ __global__ __launch_bounds__(64 * KT, 2) void wide_node_tail_kernel(WideTailArgs
             if (64 * p < cnt) {
                 // the h rows of the pair, split once for both heads (their last readers are behind the barriers of the previous pair)
                 wnt_stage_rows(a.h, ld, W, n0, a.n_nodes, cnt, 64 * p, T, c, hh, lds + lo, worst);
-                if (gated) wnt_head_pair<KT>(a, a.gate, n0, cnt, 64 * p, T, c, hh, tid, lo, lds, yg[2 * p], yg[2 * p + 1], worst);
-                wnt_head_pair<KT>(a, a.main, n0, cnt, 64 * p, T, c, hh, tid, lo, lds, ym[2 * p], ym[2 * p + 1], worst);
+                if (gated) wnt_head_pair<KT, 0>(a, a.gate, n0, cnt, 64 * p, T, c, hh, tid, lo, lds, yg[2 * p], yg[2 * p + 1], worst);
+                wnt_head_pair<KT, 1>(a, a.main, n0, cnt, 64 * p, T, c, hh, tid, lo, lds, ym[2 * p], ym[2 * p + 1], worst);
             }
         }
         // the statistics of this wave's channels, then tau in place of the gate head's y
         if (gated) {
-            wnt_instance_norm(yg, uniform_ro(a.gate.scales, 5), cnt, c, a.eps, bad);
+            wnt_instance_norm(yg, uniform_ro(a.gate.scales, 5) * (1.0f / WNT_Z_SCALE), cnt, c, a.eps, bad);
 #pragma unroll
             for (int b = 0; b < 4; ++b)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) yg[b][r] = sigmoidf_(yg[b][r]);
         }
-        wnt_instance_norm(ym, uniform_ro(a.main.scales, 5), cnt, c, a.eps, bad);
+        wnt_instance_norm(ym, uniform_ro(a.main.scales, 5) * (1.0f / WNT_Z_SCALE), cnt, c, a.eps, bad);
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
             if (32 * b + c < cnt) {
@@ -353,8 +385,8 @@ __global__ __launch_bounds__(64 * KT, 2) void wide_node_tail_kernel(WideTailArgs
 using namespace msmp;
 
 // msmp_tune("wide_tail", 1): the host layer takes this kernel at widths other than 128; 0 (default): concatenation + two row GEMMs +
-// msmp_wide_norm_blend_f32.  Faster by 22-25 % per step, but at full depth (6 gated pairs, untrained weights) the fp16-split arithmetic of
-// the node half misses the bar of test_full_depth_vs_oracle that the bf16x3 row GEMMs meet (profiles/r10a_glu_wide_node_tail.md)
+// msmp_wide_norm_blend_f32.  Faster by 22-25 % per step (profiles/r10a_glu_wide_node_tail.md).  update_net_2 is centred per graph (see the
+// head of this file), so b4 does not enter the result; full-depth figures under the switch: profiles/r28a_glu_wide_tail_centred.md
 
 static bool wide_tail_nv_ok(const char* who, int nv) {
     if (nv < 0 || nv > MSMP_MAX_VARS) {
@@ -405,15 +437,15 @@ extern "C" int msmp_wide_node_tail_f32(const float* h, const float* agg_main, co
     const int kt = (width + 31) / 32;
     const WideTailLayout L = wide_tail_layout(kt);
     auto head = [&](const float* agg, const float* packed) {
-        if (!packed) return WideTailHead{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        return WideTailHead{agg, packed + L.scales, packed + L.b3, packed + L.b4, reinterpret_cast<const half8*>(packed + L.w3),
+        if (!packed) return WideTailHead{nullptr, nullptr, nullptr, nullptr, nullptr};
+        return WideTailHead{agg, packed + L.scales, packed + L.b3, reinterpret_cast<const half8*>(packed + L.w3),
                             reinterpret_cast<const half8*>(packed + L.w4)};
     };
     WideTailArgs a{h, vars, graph_ptr, (int)n_nodes, (int)n_graphs, nv, width, ld, eps, head(agg_main, packed_main), head(agg_gate, packed_gate), out,
                    status_ptr()};
     dispatch_kt(kt, [&](auto K) {
         constexpr int KT = decltype(K)::value;
-        const long resident = resident_workgroups(device_cus(), (4 * KT + 1) * 2 * WNT_NB * 1024, KT);       // persistent (LDS: 16 KT + 4 KB of fragments)
+        const long resident = resident_workgroups(device_cus(), wnt_lds_bytes(KT), KT);       // persistent (LDS: 16 KT + 4 KB of fragments + 256 KT B)
         const unsigned grid = (unsigned)(a.n_graphs < resident ? a.n_graphs : resident);
         hipLaunchKernelGGL((wide_node_tail_kernel<KT>), dim3(grid), dim3(64 * KT), 0, (hipStream_t)stream, a);
     });
